@@ -12,11 +12,16 @@ are resident in HBM before the timed region.  Weights are the deterministic synt
 offline).  Default arithmetic (--mma bf16x6p) is fp32-class: backbone tensors are three bf16 planes whose sum IS the
 fp32 value, products keep the six cross terms down to 2^-16 (error ~2^-24, like an fp32 product), accumulation is
 fp32; Linear layers run the same six-term contraction on fp32 tensors and attention runs on the fp32 matrix pipe.
-The exact-fp32-MFMA mode (`exact_f32_mode`) and the 16-bit-operand throughput mode (`throughput_mode`, bf16x3p) are
-timed beside it on the same step.
+
+A plain run sets up, warms up, times --steps steps and prints the line; the legs of that line that need runs of their
+own are null unless --full is given.  With --full the exact-fp32-MFMA mode (`exact_f32_mode`) and the 16-bit-operand
+throughput mode (`throughput_mode`, bf16x3p) are timed beside it on the same step,
 `roofline` is measured live with HIP events (torch.cuda.Event on the launch stream) around every C-ABI
-launch in one extra instrumented step after the timed region; `cpu_baseline` times the CPU oracle
-(a port of the reference path) on a bounded sample on the host cores.
+launch in one extra instrumented step after the timed region, and `cpu_baseline` times the CPU oracle
+(a port of the reference path) on a bounded sample on the host cores (the --no-* options switch single legs off).
+
+--dump-outputs DIR writes what the last timed step computed (model outputs, losses, a fixed sample of every gradient
+tensor and every gradient tensor's norm) as DIR/<name>.npy, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -330,6 +335,52 @@ def cpu_baseline(T_sample: int, res: int, L: int, T_full: int, threads: int, rep
             "lines": lines}
 
 
+GRAD_SAMPLE = 4096          # elements per gradient tensor in grad_sample.npy (tensors this small are written whole)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ts, total, out_dir: str) -> dict:
+    """What a caller of the timed step receives after its LAST step, as out_dir/<name>.npy: the model outputs and aux
+    outputs (kept before the criterion edits pred_boxes), the weighted total and every loss term, and the gradients —
+    every tensor's L2 norm (float64, grad_norm.npy) and a sample of each drawn at indices from a fixed seed
+    (grad_sample.npy, named_parameters order), so the whole set stays far below 64 MB.  Returns name -> shape."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def put(name, t):
+        t = t.detach().cpu()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        arrays[name] = t.numpy()
+
+    for k, v in ts.last_out.items():
+        if k != "aux":
+            put(k, v)
+    for i, aux in enumerate(ts.last_out["aux"]):
+        for k, v in aux.items():
+            put(f"aux{i}_{k}", v)
+    put("loss_total", total.reshape(1).double())
+    for k, v in ts.last_losses.items():
+        put(k if k.startswith("loss_") else f"loss_{k}", v.reshape(-1).double())
+    gen = torch.Generator().manual_seed(20261016)
+    norms, samples = [], []
+    for _, g in ts.gradients().items():
+        flat = g.reshape(-1)
+        norms.append(flat.double().norm())
+        if flat.numel() <= GRAD_SAMPLE:
+            samples.append(flat.float())
+        else:
+            idx = torch.randint(0, flat.numel(), (GRAD_SAMPLE,), generator=gen)
+            samples.append(flat[idx.to(flat.device)].float())
+    put("grad_norm", torch.stack(norms))
+    put("grad_sample", torch.cat(samples))
+    size = sum(a.nbytes for a in arrays.values())
+    assert size <= DUMP_LIMIT_BYTES, f"--dump-outputs: {size} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -377,6 +428,14 @@ def main():
     ap.add_argument("--hoist-loss-plan", action="store_true",
                     help="build the loss's target-only index tensors and run its 1-element box-count all-reduce once, "
                          "outside the steps (round-3 behaviour); default: inside every timed step, as the reference does")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement of the line: the instrumented roofline / "
+                         "per-kernel steps, the other arithmetic modes, the optimizer tail, the evaluation path, the input "
+                         "side, the hot-path-only exchange at N > 1 and the CPU baseline (each can be switched off by its "
+                         "--no-* option); default: only the timed steps, those entries are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64): outputs, aux "
+                         "outputs, losses, a seeded sample of every gradient tensor and every gradient tensor's L2 norm")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -424,6 +483,7 @@ def main():
     ts = TrainStep(dev, args.config, rank=rank, train=not args.eval_mode, roberta_dummy=roberta_dummy,
                    force_comm=force_comm, loss_plan_inside=not (args.hoist_loss_plan or args.graph),   # (a capture cannot hold the plan's H2D copy)
                    clips=clips, pipeline_prefix=pipeline)
+    ts.keep_outputs = bool(args.dump_outputs)   # (every step keeps a copy of its outputs: the last timed one is dumped)
     model, criterion, wd, reducer, arena = ts.model, ts.criterion, ts.wd, ts.reducer, ts.arena
     videos, mask, targets = ts.videos, ts.videos.mask, ts.targets
     uniform_w = ts.uniform_w
@@ -489,7 +549,7 @@ def main():
     t0 = time.perf_counter()
     c0 = time.process_time()
     for _ in range(args.steps):
-        step()
+        last_total = step()
     pstats1 = dict(ts.model.vis_encoder[0].prefix_stats)
     host_s = time.perf_counter() - t0  # host time to ENQUEUE the steps (no sync): ~= elapsed means launch-bound
     host_cpu_s = time.process_time() - c0  # CPU time of all threads of this process while enqueuing (python + autograd
@@ -502,12 +562,19 @@ def main():
     # exposed gradient-exchange time: device time between the last backward kernel and the averaged gradients
     # (all-reduces that did not finish under the backward pass + the 1/world scaling), rank 0, mean over the timed steps
     exposed_ms = (sum(a.elapsed_time(b) for a, b in comm_events) / len(comm_events)) if comm_events else None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(ts, last_total, args.dump_outputs)
+
+    # Everything below measures something other than the headline and runs with --full only.
+    full = args.full
+    profile = full and not args.no_profile
 
     if graphed is not None:  # the instrumented / side measurements below time individual launches: eager mode
         reducer.defer(False)
         step = eager_step
     roof, kernels, gemm_shapes = None, None, None
-    if not args.no_profile:
+    if profile:
         # Two extra instrumented steps; EVERY rank runs them (a step contains collectives), rank 0 records events.  They
         # bracket every launch with HIP events on the launch's own stream, launch by launch from Python (same kernels,
         # same order as the replayed plans).  (1) the step as scheduled — three streams, kernels of different streams
@@ -546,7 +613,7 @@ def main():
                 "launches": a["launches"] + b["launches"], "ms": a["ms"] + b["ms"], "flop": a["flop"] + b["flop"]}
         return fam
 
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and profile:
         agg = prof.summary()
         agg_iso = prof_iso.summary()
         kernels = {k: {"launches": v["launches"], "ms": round(v["ms"], 3),
@@ -615,7 +682,7 @@ def main():
     # (hot path 327 MB + a 498 MB stand-in for the RoBERTa gradients the reference's DDP also reduces); the same steps
     # with the hot path's own 327 MB only are timed beside it.
     hot_only = None
-    if world > 1 and roberta_dummy:
+    if full and world > 1 and roberta_dummy:
         reducer.skip_extra = True
         step()
         fence()
@@ -634,7 +701,7 @@ def main():
     # The other arithmetic modes, timed on the same step beside the headline: the exact-fp32 mode is the
     # reference's own arithmetic, bf16x6 the fp32-class split mode, bf16x3 the 16-bit-operand mode on fp32 tensors.
     exact, other_modes = None, None
-    if world == 1 and not args.no_exact:
+    if full and world == 1 and not args.no_exact:
         other_modes = {}
         notes = {"f32": "f32 (v_mfma_f32_32x32x2_f32, exact products)", "bf16x6": "fp32 tensors, 6 bf16 cross terms (fp32-class)",
                  "bf16x3": "fp32 tensors, 3 bf16 cross terms, operands split in-kernel",
@@ -690,7 +757,7 @@ def main():
     # Optimizer tail (clip_grad_norm_ + AdamW + EMA, scripts/train_net.py:134-143): NOT part of the fwd+bwd metric;
     # timed here on the gradients the last step left behind so the cost of the next stage is on record.
     opt_tail = None
-    if world == 1 and not args.no_optim:
+    if full and world == 1 and not args.no_optim:
         import copy
         from stcat_amd import optim
         named = [(n, p) for n, p in model.named_parameters() if p.grad is not None]
@@ -720,7 +787,7 @@ def main():
     # Evaluation path (engine/evaluate.py:97-119): two forward passes on the even / odd frames, device-side T x T map
     # argmax, span union, linear_interp of skipped frames — videos/s of test_net.py's inner loop on the same clip.
     eval_path = None
-    if world == 1 and not args.no_exact:
+    if full and world == 1 and not args.no_exact:
         from stcat_amd.pipeline import build_postprocessors, evaluate_video
         post = build_postprocessors()
         was_training = model.training
@@ -762,7 +829,7 @@ def main():
     # fused into the stem's gather.  PCIe-inclusive rate of the step when every step first uploads its frames from
     # pinned host memory: 38.5 MB (uint8) instead of 154 MB (the normalised fp32 tensor).  Never `value`.
     loader = None
-    if world == 1 and not args.no_exact:
+    if full and world == 1 and not args.no_exact:
         u8_host = torch.randint(0, 256, (T, res, res, 3), dtype=torch.uint8).pin_memory()
         f32_host = torch.empty(T, 3, res, res, dtype=torch.float32).pin_memory()
         loader = {"h2d_MB_uint8": round(u8_host.numel() / 1e6, 1), "h2d_MB_fp32": round(f32_host.numel() * 4 / 1e6, 1)}
@@ -820,8 +887,10 @@ def main():
                           "previous step computes (stcat_amd/loader.py)")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # N=1 only: other ranks would idle at the barrier
-        cpu = cpu_baseline(min(args.cpu_sample_frames, T), res, L, T, min(os.cpu_count() or 1, args.cpu_threads))
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # N=1 only: other ranks would idle at the barrier
+        # (cores: the process's CPU budget where OMP_NUM_THREADS states one — more threads than cores only slow the oracle)
+        cores = int(os.environ.get("OMP_NUM_THREADS") or 0) or len(os.sched_getaffinity(0)) or os.cpu_count() or 1
+        cpu = cpu_baseline(min(args.cpu_sample_frames, T), res, L, T, min(cores, args.cpu_threads))
 
     if rank == 0:
         line = {
@@ -883,6 +952,8 @@ def main():
                             "all-reduce (criterion.py:175-178) — all inside every timed step since round 4",
             "kernels": kernels,
             "gemm_shapes": gemm_shapes,
+            "full": full,            # False: the side legs above (roofline .. input_side, cpu_baseline) were not run
+            "dumped_outputs": dumped,
         }
     # The JSON line must be the LAST thing on stdout.  RCCL writes a version banner through C stdio, which is
     # block-buffered when stdout is a pipe and would otherwise be flushed at process exit, AFTER the line: flush

@@ -4,8 +4,11 @@
 `emu`  : the SAME kernel sources compiled for the host SIMT emulator (tests/emu/), CPU
          tensors — checks index logic and the autograd wiring without a GPU.
 """
+import contextlib
+import fcntl
 import os
 import subprocess
+import time
 
 import pytest
 import torch
@@ -13,24 +16,100 @@ import torch
 from stcat_amd import _lib as L
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMU_SO = os.path.join(HERE, "emu", "_build", "libstcat_emu.so")
+BUILD_DIR = os.path.join(HERE, "emu", "_build")
+EMU_SO = os.path.join(BUILD_DIR, "libstcat_emu.so")
 _emu_state = {"built": False, "error": None}
 
 
+@contextlib.contextmanager
+def _file_lock(path):
+    """exclusive lock shared by every test process of this checkout (pytest-xdist workers included)"""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "a") as f:
+        fcntl.flock(f, fcntl.LOCK_EX)
+        try:
+            yield
+        finally:
+            fcntl.flock(f, fcntl.LOCK_UN)
+
+
 def _build_emu():
+    """Build the emulator library once per checkout: when the caller chose the xdist worker count, every worker reaches
+    this at the same time — one compiles under the lock (into a temporary file that replaces the library in one rename),
+    the others wait and then find it fresh."""
     if _emu_state["built"] or _emu_state["error"]:
         return
     srcs = [os.path.join(HERE, "emu", f) for f in ("hip_emu.h", "emu_main.cpp")]
     csrc = os.path.join(HERE, "..", "stcat_amd", "csrc")
     srcs += [os.path.join(csrc, f) for f in os.listdir(csrc)]
     srcs.append(os.path.join(HERE, "..", "include", "stcat_hip.h"))
-    fresh = os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(s) for s in srcs)
-    if not fresh:
-        r = subprocess.run(["sh", os.path.join(HERE, "emu", "build_emu.sh")], capture_output=True, text=True)
-        if r.returncode != 0:
-            _emu_state["error"] = r.stderr[-2000:]
-            return
+    with _file_lock(os.path.join(BUILD_DIR, ".build.lock")):
+        fresh = os.path.exists(EMU_SO) and all(os.path.getmtime(EMU_SO) >= os.path.getmtime(s) for s in srcs)
+        if not fresh:
+            tmp = f"{EMU_SO}.{os.getpid()}.tmp"
+            r = subprocess.run(["sh", os.path.join(HERE, "emu", "build_emu.sh"), tmp], capture_output=True, text=True)
+            if r.returncode != 0:
+                _emu_state["error"] = r.stderr[-2000:]
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+                return
+            os.replace(tmp, EMU_SO)
     _emu_state["built"] = True
+
+
+HEAVY_TEST_BYTES = 4 << 30   # peak host memory of one model-level CPU test (measured: 2.7 - 3.1 GB at C1 / tiny clips)
+
+
+def _host_memory_bytes():
+    """memory this process may use: the machine's, or its cgroup's limit where that is lower"""
+    with open("/proc/meminfo") as f:
+        total = next(int(l.split()[1]) * 1024 for l in f if l.startswith("MemTotal:"))
+    for path in ("/sys/fs/cgroup/memory.max", "/sys/fs/cgroup/memory/memory.limit_in_bytes"):
+        try:
+            with open(path) as f:
+                v = f.read().strip()
+        except OSError:
+            continue
+        if v.isdigit():
+            total = min(total, int(v))
+    return total
+
+
+def heavy_test_slots():
+    """how many model-level CPU tests may hold memory at once: 60 % of the host (or cgroup) memory in 4 GB slots"""
+    return max(1, int(0.6 * _host_memory_bytes()) // HEAVY_TEST_BYTES)
+
+
+_slot_held = [False]
+
+
+@contextlib.contextmanager
+def host_memory_slot():
+    """Hold one of heavy_test_slots() slots for the duration of a model-level CPU test.  With as many pytest-xdist
+    workers as the caller asks for, every worker would otherwise start one of these ~3 GB tests at once (they are
+    scheduled first); beyond the slots, a worker waits here.  Slots are file locks, released when the process ends."""
+    if _slot_held[0]:                # (nested: this process already holds a slot)
+        yield
+        return
+    slots = heavy_test_slots()
+    os.makedirs(BUILD_DIR, exist_ok=True)
+    while True:
+        for i in range(slots):
+            f = open(os.path.join(BUILD_DIR, f".memory_slot_{i}.lock"), "a")
+            try:
+                fcntl.flock(f, fcntl.LOCK_EX | fcntl.LOCK_NB)
+            except OSError:
+                f.close()
+                continue
+            _slot_held[0] = True
+            try:
+                yield
+            finally:
+                _slot_held[0] = False
+                fcntl.flock(f, fcntl.LOCK_UN)
+                f.close()
+            return
+        time.sleep(0.5)
 
 
 def use_emu():

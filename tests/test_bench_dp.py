@@ -44,7 +44,8 @@ def test_bench_two_ranks_gloo_c3():
     env = dict(os.environ, STCAT_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29537", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-exact", "--no-optim", "--no-profile"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-exact", "--no-optim",
+           "--no-profile"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, _child_errors(r.stderr)
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -60,7 +61,7 @@ def test_bench_two_ranks_gloo_c3():
 
 @pytest.mark.gpu
 def test_bench_default_line_over_the_rccl_path_single_rank():
-    """ONE run of the default command line (all side measurements on) at C1 with STCAT_FORCE_COMM=1, which drives the
+    """ONE run of the --full command line (all side measurements on) at C1 with STCAT_FORCE_COMM=1, which drives the
     complete RCCL path (process group on the device, barriers, bucketed async all-reduce + wait + mean, the loss's
     box-count all-reduce inside every step) with one rank — what a 1-GPU box can check of the N>1 configuration:
       * the bench line is the LAST stdout line although RCCL prints a banner through C stdio;
@@ -72,7 +73,7 @@ def test_bench_default_line_over_the_rccl_path_single_rank():
         pytest.skip("no GPU")
     env = dict(os.environ, STCAT_FORCE_COMM="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     env.pop("STCAT_DIST_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--config", "C1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--config", "C1", "--full",
            "--no-cpu-baseline", "--no-optim", "--roberta-dummy"]   # reference-sized message: 824 MB
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -105,3 +106,36 @@ def test_bench_graph_option_still_runs():
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     assert d["value"] > 0 and d["config"]["launch"] == "one hipGraph per step"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and leaves every side leg null; --dump-outputs writes what the
+    last timed step computed — outputs, losses, gradient norms and a seeded gradient sample — as float32 / float64 .npy
+    files well under 64 MB."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--config", "C1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=420, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-2 * d["value"]
+    assert d["unit"] == "videos/sec" and d["higher_is_better"] is True and d["dtype"].startswith("f32-class")
+    for k in ("roofline", "cpu_baseline", "exact_f32_mode", "throughput_mode", "near_f32_mode", "other_modes",
+              "optimizer_tail", "eval_path", "input_side", "kernels", "gemm_shapes", "hot_path_only_exchange"):
+        assert d[k] is None, k
+    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(d["dumped_outputs"]) == set(files)
+    assert {"pred_boxes", "pred_sted", "pred_actioness", "weights", "loss_total", "loss_sted", "grad_norm",
+            "grad_sample"} <= set(files)
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    for name, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    T = 8
+    assert files["pred_boxes"].shape[-1] == 4 and files["pred_boxes"].size % T == 0
+    assert files["loss_total"].shape == (1,) and files["loss_total"][0] > 0
+    assert len(files["grad_norm"]) > 500 and (files["grad_norm"] > 0).any()

@@ -21,7 +21,17 @@ from oracle import stcat_oracle as O
 from stcat_amd import synth
 from stcat_amd.misc import BoxList, NestedTensor
 from stcat_amd.pipeline import SyntheticText, build_model, build_postprocessors
-from tests.backends import close, use_emu, use_hip
+from tests.backends import close, host_memory_slot, use_emu, use_hip
+
+
+@pytest.fixture(autouse=True)
+def _host_memory_slot(request):
+    """the CPU tests of this module are model-level (~3 GB each): bounded by the host's memory, whatever -n is"""
+    if request.node.get_closest_marker("gpu") is not None:
+        yield
+        return
+    with host_memory_slot():
+        yield
 
 OUT_TOL = 1e-3
 GRAD_TOL = 1e-3

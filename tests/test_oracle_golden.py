@@ -9,7 +9,16 @@ import torch
 from oracle import stcat_oracle as O
 from stcat_amd import synth
 
+from tests.backends import host_memory_slot
 from tests.golden.make_golden import sub  # same deterministic sub-sampling
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _host_memory_slot():
+    """the tests of this module share the oracle's C1 forward with its autograd graph (~3 GB, module fixture `c1`): a
+    worker holds one of the host's memory slots from before that fixture is built until it is released, whatever -n is"""
+    with host_memory_slot():
+        yield
 
 
 def _load(golden_dir, name):

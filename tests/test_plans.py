@@ -8,7 +8,17 @@ import torch
 from stcat_amd import _lib, ops, plans, synth
 from stcat_amd.misc import BoxList, NestedTensor
 from stcat_amd.pipeline import SyntheticText, build_model
-from tests.backends import use_emu
+from tests.backends import host_memory_slot, use_emu
+
+
+@pytest.fixture(autouse=True)
+def _host_memory_slot(request):
+    """the CPU tests of this module are model-level (~3 GB each): bounded by the host's memory, whatever -n is"""
+    if request.node.get_closest_marker("gpu") is not None:
+        yield
+        return
+    with host_memory_slot():
+        yield
 
 
 def _build(dev, L=5, train=False):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 per-kernel summary of a short bench run -> gpurun_out/kernel_stats.csv (+ top list on stdout)
 R=$PWD; cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/ks
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o b -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-exact --no-optim > /dev/null 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o b -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-exact --no-optim > /dev/null 2>&1
 cd $R; mkdir -p gpurun_out; cp /tmp/ks/*kernel_stats.csv gpurun_out/kernel_stats.csv
 python - <<'PY'
 import csv

@@ -12,7 +12,7 @@ if [ "$2" != "notests" ]; then
   grep -E "gradient report|^[0-9.]+s (call|setup)|passed|failed|^FAILED|^ERROR" $O/gpu_tests_full.log | cut -c1-420 > $O/gpu_tests.log; tail -3 $O/gpu_tests.log
   timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 > $O/smoke.log; tail -1 $O/smoke.log
 fi
-timeout 1200 python bench.py 2>&1 | tail -1 > $O/bench_line.json; cut -c1-300 $O/bench_line.json
+timeout 1200 python bench.py --full 2>&1 | tail -1 > $O/bench_line.json; cut -c1-300 $O/bench_line.json
 B="python $R/bench.py --no-cpu-baseline --no-exact --no-optim"
 P='import json,sys; d=json.loads(sys.stdin.readline()); print({k:d.get(k) for k in ("ms_per_step","host_enqueue_ms_per_step","host_cpu_ms_per_step","exposed_comm_ms_per_step","n_gpus")})'
 {

@@ -2,7 +2,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r06j
 mkdir -p $O
-timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "default bench rc=$?" > $O/summary.txt
 B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-exact --no-optim --no-profile"
 run() { name=$1; shift; env "$@" timeout 600 $B > $O/bench_$name.json 2> $O/bench_$name.err; }

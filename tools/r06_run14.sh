@@ -2,7 +2,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r06m
 mkdir -p $O
-timeout 1500 python bench.py 2> $O/bench.err | tail -1 > $O/bench_line.json
+timeout 1500 python bench.py --full 2> $O/bench.err | tail -1 > $O/bench_line.json
 python -c "
 import json
 d=json.loads(open('$O/bench_line.json').read())
