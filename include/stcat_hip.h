@@ -40,6 +40,15 @@ int stcat_get_mma_mode(void);
 /* power-of-two operand scales of mode 6 (defaults 6 and 16: profiles/r04_plane_range_report.log); which: 0 weight, 1 gradient */
 int stcat_set_f16_scales(int weight_log2, int grad_log2);
 int stcat_get_f16_scale(int which);
+/* Deterministic mode (process-wide, off by default; STCAT_DETERMINISTIC=1 in the environment turns it on when the library
+ * is loaded).  On: every float sum of an entry point runs in an order fixed by the problem shape, the mma mode and the
+ * device's CU count, never by arrival order, so equal inputs give equal bits run to run.  An entry point that has no
+ * ordered form for a call FAILS (-1, stcat_last_error() names it and what it needs) instead of falling back to a float
+ * atomic: stcat_pl_conv_wgrad[_ws] without / with too small a workspace when its reduction is split, stcat_grad_sqnorm
+ * over more than one chunk (use stcat_grad_sqnorm_ws), stcat_map2d_*_bwd, stcat_debug_pl_flags bit 0x4000.  Off: nothing
+ * changes.  Not stream-ordered (host state, like the mma mode); every mma mode is supported. */
+int stcat_set_deterministic(int on);
+int stcat_get_deterministic(void);
 /* tuning/test hook: force the implicit-GEMM block tile (128x128, 128x64, 64x64; 0,0 = heuristic) */
 int stcat_debug_force_tile(int bm, int bn);
 /* stream-K scheduling of the split-bf16 forward GEMM (opt-in experiment): 1 whenever legal,
@@ -398,6 +407,10 @@ int stcat_stg_loss_bwd(const float* boxes, const long* rows, const float* tgt, c
 int stcat_optim_table_entry_bytes(void);
 int stcat_grad_sqnorm(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                       float* out_sq, void* stream);
+/* ... with a caller-owned workspace of ws_floats >= n_chunks floats: chunks store their partial sums, one workgroup adds
+ * them in chunk order (no float atomics; the form the deterministic mode requires) */
+int stcat_grad_sqnorm_ws(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
+                         float* out_sq, float* ws, long ws_floats, void* stream);
 int stcat_adamw_ema_step(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                          const float* sqnorm, const float* lr, const float* wd, int n_groups, float beta1,
                          float beta2, float eps, int step, float max_norm, float ema_decay, void* stream);

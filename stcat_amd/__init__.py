@@ -20,6 +20,17 @@ from . import synth  # noqa: F401  (pure numpy/torch helpers; no GPU needed)
 __version__ = "0.1.0"
 
 
+def set_deterministic(on: bool) -> None:
+    """Deterministic mode of the kernel library (see stcat_amd._lib.set_deterministic)."""
+    from . import _lib
+    _lib.set_deterministic(on)
+
+
+def is_deterministic() -> bool:
+    from . import _lib
+    return _lib.is_deterministic()
+
+
 def install():
     """Rebind the reference's factory seam.  Requires the reference package ``models``
     to be importable; must run before ``STCATNet`` is constructed."""

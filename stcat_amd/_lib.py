@@ -67,6 +67,7 @@ SIGNATURES: Dict[str, str] = {
     "stcat_map2d_pool_bwd": "pppiiiis",
     "stcat_rowscale": "pplii" + "s",
     "stcat_grad_sqnorm": "pppiips",
+    "stcat_grad_sqnorm_ws": "pppiippls",
     "stcat_adamw_ema_step": "pppiipPPifffiffs",
     "stcat_grad_clip_scale": "pppiipfs",
     "stcat_ema_update": "pppiifs",
@@ -97,6 +98,8 @@ SIGNATURES: Dict[str, str] = {
     "stcat_stream_destroy": "P",
     "stcat_set_mma_mode": "i",
     "stcat_get_mma_mode": "",
+    "stcat_set_deterministic": "i",
+    "stcat_get_deterministic": "",
     "stcat_set_f16_scales": "ii",
     "stcat_get_f16_scale": "i",
     # launch plans (csrc/launch_plan.h): P = host pointer, u = unsigned 64-bit, S = C string
@@ -184,6 +187,26 @@ def get_mma_mode() -> str:
     return _mode_cache
 
 
+_det_cache = (None, False)    # (library handle, mode): the plan signature asks once per node, a ctypes call each is too dear
+
+
+def set_deterministic(on: bool) -> None:
+    """Process-wide deterministic mode (off by default; STCAT_DETERMINISTIC=1 turns it on when the library is loaded):
+    every float sum of a training step runs in an order fixed by shapes, the mma mode and the CU count, so two runs from
+    one seed give the same bits.  While it is on, an entry point without an ordered form raises instead of falling back
+    to float atomics (the contract of torch.use_deterministic_algorithms).  Launch plans recorded in one mode are not
+    replayed in the other (the mode is part of the plan signature)."""
+    call("stcat_set_deterministic", 1 if on else 0)     # (call() drops the cached mode)
+
+
+def is_deterministic() -> bool:
+    global _det_cache
+    lib = load()
+    if _det_cache[0] is not lib:
+        _det_cache = (lib, bool(lib.stcat_get_deterministic()))
+    return _det_cache[1]
+
+
 def f16_grad_scale() -> float:
     """factor carried by every GRADIENT plane in mode f16x3p (1.0 in every other mode): tools / op tests that build
     gradient planes themselves multiply by it; the product path scales where gradients enter the backbone (pl_act_bwd)"""
@@ -223,8 +246,11 @@ RECORDER = None  # stcat_amd.plans.Recorder while a launch plan is being recorde
 
 
 def call(name: str, *args) -> None:
+    global _det_cache
     lib = load()
     rc = getattr(lib, name)(*args)
+    if name == "stcat_set_deterministic":
+        _det_cache = (None, False)      # re-read from the library: the setter may refuse
     if rc != 0:
         msg = lib.stcat_last_error()
         raise StcatHipError(f"{name} failed (rc={rc}): {msg.decode() if msg else ''}")

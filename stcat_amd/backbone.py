@@ -795,7 +795,7 @@ class Backbone(nn.Module):
         """what a computed prefix depends on besides the frames: the arithmetic mode (plane count AND element type), the
         static tables (FrozenBN folds / weight planes: plans.STATIC_EPOCH moves with load_state_dict / .to()) and how many
         blocks are frozen"""
-        return (ops.L.get_mma_mode(), ops.L.plane_count(), plans.STATIC_EPOCH, len(_prefix_blocks(self.body)), _prefix_range())
+        return (ops.L.get_mma_mode(), ops.L.is_deterministic(), ops.L.plane_count(), plans.STATIC_EPOCH, len(_prefix_blocks(self.body)), _prefix_range())
 
     def _take(self, frames: torch.Tensor):
         """the prefix computed for exactly these frames, or None; the current stream is ordered behind it"""

@@ -855,6 +855,37 @@ __global__ void __launch_bounds__(256) pl_colsum_kernel(const __bf16* h, const _
   }
 }
 
+// Deterministic mode, form "no split": a workgroup owns 32 columns (4 groups of 8); its 64 row lanes walk the rows
+// m = lane, lane + 64, ... in order and are summed by a fixed tree, so every out[n] has ONE adder and an order fixed by
+// (M, N).  (The kernel above with a single row chunk does the same on N / 256 workgroups only: 2 ms at 12544 x 2048.)
+__global__ void __launch_bounds__(256) pl_colsum_det_kernel(const __bf16* h, const __bf16* l, float* out, int M, int N, int np) {
+  __shared__ float red[64][32 + 1];
+  const int cg = threadIdx.x & 3, rl = threadIdx.x >> 2;
+  const int n = blockIdx.x * 32 + cg * 8;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (n < N) {
+    for (int m = rl; m < M; m += 64) {
+      STCAT_UNROLL
+      for (int pi = 0; pi < 3; ++pi) {
+        if (pi < np) {
+          const bf16x8 v = *reinterpret_cast<const bf16x8*>(stcat_plane(h, l, pi) + (long)m * N + n);
+          STCAT_UNROLL
+          for (int e = 0; e < 8; ++e) acc[e] += (float)v[e];
+        }
+      }
+    }
+  }
+  STCAT_UNROLL
+  for (int e = 0; e < 8; ++e) red[rl][cg * 8 + e] = acc[e];
+  __syncthreads();
+  for (int s = 32; s >= 1; s >>= 1) {
+    for (int i = threadIdx.x; i < s * 32; i += 256) red[i >> 5][i & 31] += red[(i >> 5) + s][i & 31];
+    __syncthreads();
+  }
+  const int c = blockIdx.x * 32 + threadIdx.x;
+  if (threadIdx.x < 32 && c < N) out[c] += red[0][threadIdx.x];
+}
+
 __global__ void __launch_bounds__(256) maxpool3x3s2_pl_kernel(const float* x, __bf16* yh, __bf16* yl, int n, int H, int W,
                                                              int C, int OH, int OW, int np) {
   const int c8n = C / 8;

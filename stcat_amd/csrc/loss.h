@@ -167,6 +167,19 @@ __global__ void __launch_bounds__(256) stg_loss_fwd_kernel(StgLossParams p) {
   }
 }
 
+// deterministic mode: total += sum_l (sum_k wmat[k][l] * vec[k][l]), the inner sums as stg_loss_fwd_kernel forms them,
+// the outer one in layer order by one thread
+__global__ void stg_loss_total_kernel(const float* wmat, const float* vec, float* total, int nl) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float sum = 0.f;
+  for (int l = 0; l < nl; ++l) {
+    float tot = 0.f;
+    for (int k = 0; k < 5; ++k) tot += wmat[k * nl + l] * vec[k * nl + l];
+    sum += tot;
+  }
+  *total += sum;
+}
+
 __global__ void __launch_bounds__(256) stg_loss_bwd_kernel(StgLossParams p) {
   __shared__ float red[8];
   const int l = blockIdx.x, tid = threadIdx.x;

@@ -37,7 +37,8 @@ struct OptHyper {
 };
 
 __global__ void __launch_bounds__(256) grad_sqnorm_kernel(const OptTensor* tab, const int* chunk_tensor,
-                                                          const long* chunk_off, int chunk, float* out) {
+                                                          const long* chunk_off, int chunk, float* out,
+                                                          float* partial) {
   __shared__ float part[4];
   const OptTensor t = tab[chunk_tensor[blockIdx.x]];
   const long lo = chunk_off[blockIdx.x];
@@ -59,7 +60,25 @@ __global__ void __launch_bounds__(256) grad_sqnorm_kernel(const OptTensor* tab, 
   acc = stcat_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
+  if (threadIdx.x == 0) {
+    const float s = part[0] + part[1] + part[2] + part[3];
+    if (partial) partial[blockIdx.x] = s;   // deterministic form: store, grad_sqnorm_sum_kernel adds in chunk order
+    else atomicAdd(out, s);
+  }
+}
+
+// out = sum of partial[0 .. n) in a fixed order: thread t adds partial[t], partial[t + 256], ... then a fixed tree
+__global__ void __launch_bounds__(256) grad_sqnorm_sum_kernel(const float* partial, int n, float* out) {
+  __shared__ float red[256];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = red[0];
 }
 
 static __device__ __forceinline__ void stcat_adamw_one(float& p, float g, float& m, float& v, float* ema, float coef,

@@ -85,8 +85,70 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const float* dy, con
   r1[0] = ab.x; r1[1] = ab.y; r1[2] = ab.z; r1[3] = ab.w;
   __syncthreads();
   const int c = threadIdx.x;
+  if (!dgamma) return;  // deterministic mode: layernorm_bwd_affine_det_kernel owns dgamma / dbeta
   atomicAdd(dgamma + c, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
   atomicAdd(dbeta + c, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+}
+
+// ---------------------------------------------------------------------------------
+// Deterministic mode (stcat_set_deterministic): the column reductions WITHOUT a split over rows between workgroups.
+// Form "no split": a workgroup owns 32 columns; its 16 row lanes walk the rows m = lane, lane + 16, ... in order and are
+// summed by a fixed tree in LDS, so every destination has exactly ONE adder and an order fixed by (M, N) alone.  (A
+// store-and-sum over row chunks would keep more CUs busy but needs a caller-owned workspace these entry points do not
+// take; the price is measured in DESIGN.md section 7.)
+// ---------------------------------------------------------------------------------
+#define STCAT_DET_COLS 32
+#define STCAT_DET_LANES 16
+static __device__ __forceinline__ float stcat_det_lane_tree(float v, float (*red)[STCAT_DET_COLS + 1], int rl, int cl) {
+  red[rl][cl] = v;
+  __syncthreads();
+  for (int s = STCAT_DET_LANES / 2; s >= 1; s >>= 1) {
+    if (rl < s) red[rl][cl] += red[rl + s][cl];
+    __syncthreads();
+  }
+  return red[0][cl];
+}
+
+// dgamma[c] += sum_m dy * xhat, dbeta[c] += sum_m dy with xhat recomputed as layernorm_bwd_kernel does (D = 256)
+__global__ void __launch_bounds__(STCAT_DET_COLS * STCAT_DET_LANES)
+    layernorm_bwd_affine_det_kernel(const float* dy, const float* x, const float* res, const float* mean, const float* rstd,
+                                    float* dgamma, float* dbeta, int M, DropParams drop) {
+  drop = stcat_drop_resolve(drop);
+  __shared__ float red[STCAT_DET_LANES][STCAT_DET_COLS + 1];
+  const int cl = threadIdx.x % STCAT_DET_COLS, rl = threadIdx.x / STCAT_DET_COLS, c = blockIdx.x * STCAT_DET_COLS + cl;
+  float ag = 0.f, ab = 0.f;
+  for (int row = rl; row < M; row += STCAT_DET_LANES) {
+    const long i = (long)row * 256 + c;
+    float v = x[i];
+    if (drop.thresh) v *= stcat_drop_mul(drop, (unsigned long long)i);
+    if (res) v += res[i];
+    const float d = dy[i];
+    ag += d * ((v - mean[row]) * rstd[row]);
+    ab += d;
+  }
+  ag = stcat_det_lane_tree(ag, red, rl, cl);
+  __syncthreads();
+  ab = stcat_det_lane_tree(ab, red, rl, cl);
+  if (rl == 0) {
+    dgamma[c] += ag;
+    dbeta[c] += ab;
+  }
+}
+
+// out[n] += sum_m a[m][n] * (b ? b[m][n] : 1)
+__global__ void __launch_bounds__(STCAT_DET_COLS * STCAT_DET_LANES)
+    colsum_det_kernel(const float* a, const float* b, float* out, int M, int N) {
+  __shared__ float red[STCAT_DET_LANES][STCAT_DET_COLS + 1];
+  const int cl = threadIdx.x % STCAT_DET_COLS, rl = threadIdx.x / STCAT_DET_COLS, n = blockIdx.x * STCAT_DET_COLS + cl;
+  float acc = 0.f;
+  if (n < N) {
+    for (int m = rl; m < M; m += STCAT_DET_LANES) {
+      const float v = a[(long)m * N + n];
+      acc += b ? v * b[(long)m * N + n] : v;
+    }
+  }
+  acc = stcat_det_lane_tree(acc, red, rl, cl);
+  if (rl == 0 && n < N) out[n] += acc;
 }
 
 // out[n] += sum_m a[m][n] * (b ? b[m][n] : 1)      (bias gradients; affine gradients)

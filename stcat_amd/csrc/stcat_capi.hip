@@ -3,6 +3,8 @@
 // (and, with -DSTCAT_EMU, by host clang against tests/emu/hip_emu.h for index-logic tests).
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 #include "../../include/stcat_hip.h"
 #include "attention.h"
@@ -87,6 +89,18 @@ int g_pl_f16 = 0;    // mode 6 (f16x3p): the two planes hold IEEE fp16 (22 signi
 int g_f16_wlog = 6, g_f16_glog = 16;   // its operand scales: weight planes hold w * 2^wlog, gradient planes dy * 2^glog
 inline int pl_np_arg() { return g_pl_np | (g_pl_f16 ? 0x100 : 0); }   // what the element-wise plane kernels take as `np`
 
+// Deterministic mode (stcat_set_deterministic; STCAT_DETERMINISTIC=1 when the library is loaded): every float sum of an
+// entry point runs in an order fixed by shapes, the mma mode and the CU count; an entry point that has no such form
+// FAILS (det_refuse) instead of falling back to a float atomic with several adders.  Off: nothing changes.
+static int env_deterministic() {
+  const char* e = getenv("STCAT_DETERMINISTIC");
+  return (e && *e && strcmp(e, "0") != 0) ? 1 : 0;
+}
+int g_deterministic = env_deterministic();
+static int det_refuse(const char* entry, const char* needs) {
+  return fail("%s: refused in deterministic mode (stcat_set_deterministic): %s", entry, needs);
+}
+
 #define STCAT_TILE_SWITCH(KERNEL, GRID)                                                        \
   if (BM == 128 && BN == 128) {                                                                \
     STCAT_LAUNCH((KERNEL<128, 128>), GRID, dim3(256), 0, st, p);                               \
@@ -160,6 +174,10 @@ static bool sk_wanted(const IgemmParams& p, int workers) {
 // add into the zeroed output.  Only when the epilogue is bias / residual (no scale, ReLU, mask, second output).
 static bool g_acc_output = false;  // set by the *_acc entries around the launch: C already holds the value to add onto
 static int skinny_splits(const IgemmParams& p) {
+  // deterministic mode, form "no split": one workgroup walks the whole reduction of its tile.  The accumulating
+  // entries keep the adding epilogue with ONE slice (one adder per destination and launch: order-free).
+  if (g_deterministic)
+    return (g_acc_output && bs_ok(p) && p.M <= 128 && p.K >= 128 && !p.scale && !p.relu && !p.mask && !p.C2 && p.c_group >= p.M) ? 1 : 0;
   const int min_k = g_acc_output ? 128 : 1024;   // without the memset launch a 4-K-tile reduction is worth splitting too
   if (!(bs_ok(p) && p.M <= 128 && p.K >= min_k && !p.scale && !p.relu && !p.mask && !p.C2 && p.c_group >= p.M)) return 0;
   const int nk = p.K / 32;
@@ -263,9 +281,16 @@ int launch_wgrad(IgemmParams p, int rows, int cols, int red, hipStream_t st) {
   const bool bs = g_mma_mode != 0 && p.a_bytes != 0xFFFFFFFFu && p.b_bytes != 0xFFFFFFFFu;
   // 8-wave 256x128 tile, ONE workgroup per CU and at most one round of them: the most efficient configuration
   // measured for long reductions (tools/bench_quant.py); needs Cout % 256 == 0 (layer3/4, the FFN)
-  const bool big8 = bs && g_mma_mode == 2 && (rows % 256 == 0) && (p.g.C % 128 == 0) &&
-                    (g_force_bm == 256 || (!g_force_bm && red >= 4096));
-  const bool big = (rows % 128 == 0) && (p.g.C % 128 == 0) && g_force_bm != 64;
+  bool big8 = bs && g_mma_mode == 2 && (rows % 256 == 0) && (p.g.C % 128 == 0) &&
+              (g_force_bm == 256 || (!g_force_bm && red >= 4096));
+  bool big = (rows % 128 == 0) && (p.g.C % 128 == 0) && g_force_bm != 64;
+  // deterministic mode, form "no split": grid.z = 1, so every dW element (and every bias row sum) has ONE adder.  The
+  // reduction is then as long as the launch has pixels; small tiles put four times the workgroups on it where the big
+  // ones would leave most CUs idle (the choice depends on the shape alone).
+  if (g_deterministic) {
+    big8 = false;
+    if (!g_force_bm && (rows / 128) * (cols / 128) < 256) big = false;
+  }
   const int BM = big8 ? 256 : (big ? 128 : 64), BN = big8 ? 128 : (big ? 128 : 64);
   const int tiles = (rows / BM) * (cols / BN);
   // split the reduction so that the grid is at most two full rounds of the resident slots (512 four-wave or
@@ -274,7 +299,7 @@ int launch_wgrad(IgemmParams p, int rows, int cols, int red, hipStream_t st) {
   int nsplit = slots / tiles;
   const int max_split = cdiv(red, 256);  // at least 8 K-tiles per workgroup: shorter loops are all prologue + atomics
   if (nsplit > max_split) nsplit = max_split;
-  if (nsplit < 1) nsplit = 1;
+  if (nsplit < 1 || g_deterministic) nsplit = 1;
   int chunk = cdiv(red, nsplit);
   chunk = ((chunk + 31) / 32) * 32;
   nsplit = cdiv(red, chunk);
@@ -299,6 +324,31 @@ int launch_wgrad(IgemmParams p, int rows, int cols, int red, hipStream_t st) {
     STCAT_LAUNCH((igemm_wgrad_kernel<64, 64>), grid, dim3(256), 0, st, p);
   }
   return launch_status();
+}
+
+// Deterministic mode: problems of a group that add onto the SAME output (or the same bias gradient) must not meet in
+// one launch.  Round r holds the r-th problem of every distinct output, in problem order; the rounds are launched one
+// after the other on the stream, so each destination sees its adders in problem order.
+template <class Launch>
+static int multi_rounds(const IgemmMulti& mp, int n, Launch launch) {
+  int round[8], nr = 1;
+  for (int j = 0; j < n; ++j) {
+    round[j] = 0;
+    for (int i = 0; i < j; ++i)
+      if ((mp.C[i] == mp.C[j] || (mp.rowsum[j] && mp.rowsum[i] == mp.rowsum[j])) && round[i] + 1 > round[j]) round[j] = round[i] + 1;
+    if (round[j] + 1 > nr) nr = round[j] + 1;
+  }
+  for (int r = 0; r < nr; ++r) {
+    IgemmMulti q = mp;
+    int cnt = 0;
+    for (int j = 0; j < n; ++j) {
+      if (round[j] != r) continue;
+      q.A[cnt] = mp.A[j]; q.B[cnt] = mp.B[j]; q.bias[cnt] = mp.bias[j]; q.C[cnt] = mp.C[j]; q.rowsum[cnt] = mp.rowsum[j];
+      ++cnt;
+    }
+    if (int rc = launch(q, cnt)) return rc;
+  }
+  return 0;
 }
 
 // ---- plane-format GEMMs (igemm_pl.h) ---------------------------------------------------------------------------
@@ -603,6 +653,10 @@ int launch_pl_wgrad(PlParams p, int rows, int cols, int red, hipStream_t st, flo
   const long out_floats = (long)rows * p.ldc;
   const bool use_ws = ws && nsplit > 1 && (long)nsplit * out_floats <= ws_floats && out_floats % 4 == 0 && aligned16(ws) &&
                       aligned16(p.Wf) && !(g_pl_debug & 0x4000);
+  if (g_deterministic && !use_ws && nsplit > 1)   // (nsplit == 1: one adder per element, order-free)
+    return det_refuse(ws ? "pl_conv_wgrad_ws" : "pl_conv_wgrad", (g_pl_debug & 0x4000)
+                      ? "the debug switch 0x4000 forces the atomic form"
+                      : "needs a 16-byte aligned workspace of slices x Cout x KH KW Cin floats (stcat_pl_conv_wgrad_ws)");
   p.Ws = use_ws ? ws : nullptr;
   auto finish = [&]() -> int {
     if (int rc = launch_status()) return rc;
@@ -676,6 +730,12 @@ int stcat_set_mma_mode(int mode) {
   return 0;
 }
 int stcat_get_mma_mode(void) { return g_mma_mode_raw; }
+int stcat_set_deterministic(int on) {
+  if (on && (g_pl_debug & 0x4000)) return det_refuse("set_deterministic", "stcat_debug_pl_flags bit 0x4000 (forced atomics) is set");
+  g_deterministic = on ? 1 : 0;
+  return 0;
+}
+int stcat_get_deterministic(void) { return g_deterministic; }
 int stcat_set_f16_scales(int weight_log2, int grad_log2) {
   if (weight_log2 < 0 || weight_log2 > 14 || grad_log2 < 0 || grad_log2 > 30) return fail("set_f16_scales: exponents out of range");
   g_f16_wlog = weight_log2;
@@ -1047,13 +1107,17 @@ int stcat_linear_fwd_multi(int n, const float* x0, const float* x1, const float*
   p.b_tap_stride = (unsigned)K * 4;
   p.M = M; p.N = N; p.K = K; p.ldb = K; p.ldc = N; p.ldr = 0; p.c_group = M; p.relu = 0;
   p.g = conv_geom_fwd(1, 1, K, K, 1, 1, 1, 1, 1, 0);
-  const int tiles = cdiv(M, 64) * (N / 64), splits = multi_splits(K / 32, tiles, n);
+  const int tiles = cdiv(M, 64) * (N / 64), splits = g_deterministic ? 1 : multi_splits(K / 32, tiles, n);
   p.k_chunk = cdiv(K / 32, splits);
-  const dim3 grid(tiles, n, cdiv(K / 32, p.k_chunk));
   hipStream_t st = (hipStream_t)stream;
-  if (g_mma_mode == 3) { STCAT_LAUNCH((igemm_bs_fwd_multi_kernel<3>), grid, dim3(256), 0, st, mp); }
-  else { STCAT_LAUNCH((igemm_bs_fwd_multi_kernel<2>), grid, dim3(256), 0, st, mp); }
-  return launch_status();
+  auto launch = [&](const IgemmMulti& q, int cnt) -> int {
+    const dim3 grid(tiles, cnt, cdiv(K / 32, p.k_chunk));
+    if (g_mma_mode == 3) { STCAT_LAUNCH((igemm_bs_fwd_multi_kernel<3>), grid, dim3(256), 0, st, q); }
+    else { STCAT_LAUNCH((igemm_bs_fwd_multi_kernel<2>), grid, dim3(256), 0, st, q); }
+    return launch_status();
+  };
+  if (g_deterministic) return multi_rounds(mp, n, launch);
+  return launch(mp, n);
 }
 
 // dx_j += g_j . w_j (+ add_j): the data gradients of such a group (outputs may coincide: d_x = sum_j g_j w_j)
@@ -1076,13 +1140,17 @@ int stcat_linear_dgrad_multi(int n, const float* g0, const float* g1, const floa
   q.H = 1; q.W = 1; q.C = N; q.ld = N; q.OH = 1; q.OW = 1; q.KH = 1; q.KW = 1;
   q.mul = 1; q.off = 0; q.sgn = -1; q.div = 1;
   p.g = q;
-  const int tiles = cdiv(M, 64) * (K / 64), splits = multi_splits(N / 32, tiles, n);
+  const int tiles = cdiv(M, 64) * (K / 64), splits = g_deterministic ? 1 : multi_splits(N / 32, tiles, n);
   p.k_chunk = cdiv(N / 32, splits);
-  const dim3 grid(tiles, n, cdiv(N / 32, p.k_chunk));
   hipStream_t st = (hipStream_t)stream;
-  if (g_mma_mode == 3) { STCAT_LAUNCH((igemm_bs_dgrad_multi_kernel<3>), grid, dim3(256), 0, st, mp); }
-  else { STCAT_LAUNCH((igemm_bs_dgrad_multi_kernel<2>), grid, dim3(256), 0, st, mp); }
-  return launch_status();
+  auto launch = [&](const IgemmMulti& q, int cnt) -> int {
+    const dim3 grid(tiles, cnt, cdiv(N / 32, p.k_chunk));
+    if (g_mma_mode == 3) { STCAT_LAUNCH((igemm_bs_dgrad_multi_kernel<3>), grid, dim3(256), 0, st, q); }
+    else { STCAT_LAUNCH((igemm_bs_dgrad_multi_kernel<2>), grid, dim3(256), 0, st, q); }
+    return launch_status();
+  };
+  if (g_deterministic) return multi_rounds(mp, n, launch);
+  return launch(mp, n);
 }
 
 // dw_j += g_j^T x_j, db_j += column sums of g_j: the weight gradients of such a group (N, K % 128 == 0)
@@ -1106,15 +1174,19 @@ int stcat_linear_wgrad_multi(int n, const float* g0, const float* g1, const floa
   p.g = conv_geom_fwd(1, 1, K, K, 1, 1, 1, 1, 1, 0);
   p.M = N; p.N = K; p.K = M;
   const int tiles = (N / 128) * (K / 128);
-  int nsplit = cdiv(M, 256);
+  int nsplit = g_deterministic ? 1 : cdiv(M, 256);   // deterministic mode: no split, one adder per dW element
   if (nsplit < 1) nsplit = 1;
   int chunk = ((cdiv(M, nsplit) + 31) / 32) * 32;
   p.k_chunk = chunk;
-  const dim3 grid(tiles, n, cdiv(M, chunk));
   hipStream_t st = (hipStream_t)stream;
-  if (g_mma_mode == 3) { STCAT_LAUNCH((igemm_bs_wgrad_multi_kernel<128, 3>), grid, dim3(256), 0, st, mp); }
-  else { STCAT_LAUNCH((igemm_bs_wgrad_multi_kernel<128, 2>), grid, dim3(256), 0, st, mp); }
-  return launch_status();
+  auto launch = [&](const IgemmMulti& q, int cnt) -> int {
+    const dim3 grid(tiles, cnt, cdiv(M, chunk));
+    if (g_mma_mode == 3) { STCAT_LAUNCH((igemm_bs_wgrad_multi_kernel<128, 3>), grid, dim3(256), 0, st, q); }
+    else { STCAT_LAUNCH((igemm_bs_wgrad_multi_kernel<128, 2>), grid, dim3(256), 0, st, q); }
+    return launch_status();
+  };
+  if (g_deterministic) return multi_rounds(mp, n, launch);
+  return launch(mp, n);
 }
 
 int stcat_colsum(const float* a, const float* b, float* out, int M, int N, void* stream);
@@ -1161,6 +1233,11 @@ int stcat_small_linear_bwd(const float* g, const float* x, const float* w, float
 
 int stcat_colsum(const float* a, const float* b, float* out, int M, int N, void* stream) {
   if (M <= 0 || N <= 0) return fail("colsum: M=%d N=%d", M, N);
+  if (g_deterministic) {  // form "no split": a workgroup per 32 columns, fixed tree over its row lanes (pointwise.h)
+    STCAT_LAUNCH(colsum_det_kernel, dim3(cdiv(N, STCAT_DET_COLS)), dim3(STCAT_DET_COLS * STCAT_DET_LANES), 0,
+                 (hipStream_t)stream, a, b, out, M, N);
+    return launch_status();
+  }
   int rows = cdiv(M, 512);
   if (rows < 8) rows = 8;
   STCAT_LAUNCH(colsum_kernel, dim3(cdiv(M, rows), cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, M, N,
@@ -1183,6 +1260,16 @@ int stcat_layernorm_bwd(const float* dy, const float* x, const float* res, const
   if (D != 256) return fail("layernorm: D must be 256 (got %d)", D);
   if (drop_p > 0.f && !dx) return fail("layernorm_bwd: dropout needs the dx output");
   // small M (the decoders' [T,256] states): one row per wave, so the rows of a launch are normalised in parallel
+  if (g_deterministic) {
+    // dz / dx as always, the affine gradients by the single-adder column kernel (form "no split", pointwise.h)
+    STCAT_LAUNCH(layernorm_bwd_kernel, dim3(grid_for(M, M <= 1024 ? 4 : 16, 512)), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma,
+                 mean, rstd, dz, dx, (float*)nullptr, (float*)nullptr, M, stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
+    if (int rc = launch_status()) return rc;
+    STCAT_LAUNCH(layernorm_bwd_affine_det_kernel, dim3(256 / STCAT_DET_COLS), dim3(STCAT_DET_COLS * STCAT_DET_LANES), 0,
+                 (hipStream_t)stream, dy, x, res, mean, rstd, dgamma, dbeta, M,
+                 stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
+    return launch_status();
+  }
   STCAT_LAUNCH(layernorm_bwd_kernel, dim3(grid_for(M, M <= 1024 ? 4 : 16, 512)), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma,
                mean, rstd, dz, dx, dgamma, dbeta, M, stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
   return launch_status();
@@ -1227,6 +1314,14 @@ int stcat_stg_loss_fwd(const float* boxes, const long* rows, const float* tgt, c
   if (!vec) return fail("stg_loss_fwd: vec is NULL");
   if (total && !wmat) return fail("stg_loss_fwd: total needs the weight matrix");
   q.vec = vec; q.total = total;
+  if (g_deterministic && total && nl > 1) {
+    // form "in-register chain": the layers store their five terms, one thread adds the nl weighted sums in layer order
+    q.total = nullptr;
+    STCAT_LAUNCH(stg_loss_fwd_kernel, dim3(nl), dim3(256), 0, (hipStream_t)stream, q);
+    if (int rc = launch_status()) return rc;
+    STCAT_LAUNCH(stg_loss_total_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, wmat, (const float*)vec, total, nl);
+    return launch_status();
+  }
   STCAT_LAUNCH(stg_loss_fwd_kernel, dim3(nl), dim3(256), 0, (hipStream_t)stream, q);
   return launch_status();
 }
@@ -1419,13 +1514,28 @@ int stcat_attn_q1_bwd(const float* q1, const float* q2, const float* k1, const f
 // ---- optimizer tail --------------------------------------------------------------------------------------
 int stcat_optim_table_entry_bytes(void) { return (int)sizeof(OptTensor); }
 
+// ... with a workspace of ws_floats >= n_chunks values: the chunks STORE their partial sums and one workgroup adds them
+// in chunk order with a fixed tree (form "store-and-sum"): out_sq is bit-identical run to run
+int stcat_grad_sqnorm_ws(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
+                         float* out_sq, float* ws, long ws_floats, void* stream) {
+  if (n_chunks <= 0 || chunk <= 0 || chunk % 4 != 0) return fail("grad_sqnorm_ws: bad chunking (%d x %d)", n_chunks, chunk);
+  if (!ws || ws_floats < n_chunks) return fail("grad_sqnorm_ws: the workspace must hold n_chunks = %d floats (got %ld)", n_chunks, ws_floats);
+  STCAT_LAUNCH(grad_sqnorm_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const OptTensor*)table,
+               chunk_tensor, chunk_off, chunk, (float*)nullptr, ws);
+  if (int rc = launch_status()) return rc;
+  STCAT_LAUNCH(grad_sqnorm_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, n_chunks, out_sq);
+  return launch_status();
+}
+
 int stcat_grad_sqnorm(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                       float* out_sq, void* stream) {
   if (n_chunks <= 0 || chunk <= 0 || chunk % 4 != 0) return fail("grad_sqnorm: bad chunking (%d x %d)", n_chunks, chunk);
+  if (g_deterministic && n_chunks > 1)
+    return det_refuse("grad_sqnorm", "needs a workspace of n_chunks floats (stcat_grad_sqnorm_ws)");
   hipError_t e = hipMemsetAsync(out_sq, 0, sizeof(float), (hipStream_t)stream);
   if (e != hipSuccess) return fail("grad_sqnorm: memset: %s", hipGetErrorString(e));
   STCAT_LAUNCH(grad_sqnorm_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const OptTensor*)table,
-               chunk_tensor, chunk_off, chunk, out_sq);
+               chunk_tensor, chunk_off, chunk, out_sq, (float*)nullptr);
   return launch_status();
 }
 
@@ -1480,6 +1590,8 @@ int stcat_debug_force_pl_tile(int index) {
 }
 
 int stcat_debug_pl_flags(int flags) {
+  if (g_deterministic && (flags & 0x4000) && !(flags & 0x2000))
+    return det_refuse("debug_pl_flags", "bit 0x4000 forces the atomic weight gradient");
   g_stem_pl = (flags & 0x8000) ? 0 : 1;   // bit 0x8000: the six-product modes back on the exact-fp32 stem (A/B of stem_pl.h)
   g_pl_as_skew = (flags & 0x2000) ? ((flags >> 16) & 0xffff) : 0;
   if (flags & 0x2000) flags &= 0x1fff;
@@ -1640,6 +1752,12 @@ int stcat_pl_colsum(const void* h, const void* l, float* out, int M, int N, void
   if (g_mma_mode_raw < 4) return fail("pl_colsum: plane modes only");
   int rows = cdiv(M, 256);
   if (rows < 32) rows = 32;
+  if (g_deterministic && !g_pl_f16) {   // form "no split": a workgroup per 32 columns, fixed tree over its row lanes
+    STCAT_LAUNCH(pl_colsum_det_kernel, dim3(cdiv(N, 32)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)h,
+                 (const __bf16*)l, out, M, N, pl_np_arg());
+    return launch_status();
+  }
+  if (g_deterministic) rows = M;   // (fp16 planes) one row chunk of the kernel below: one adder per column
   STCAT_LAUNCH(pl_colsum_kernel, dim3(cdiv(M, rows), cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)h,
                (const __bf16*)l, out, M, N, pl_np_arg(), rows);
   return launch_status();
@@ -1806,6 +1924,7 @@ int stcat_map2d_cells(const float* pooled, const int* cell_i, const int* cell_j,
 int stcat_map2d_cells_bwd(const float* pooled, const int* cell_i, const int* cell_j, int ncells, const float* dmap,
                           float* dpooled, int b, int N, int D, void* stream) {
   if (ncells <= 0 || b <= 0 || N <= 0 || D <= 0) return fail("map2d_cells_bwd: bad shape");
+  if (g_deterministic) return det_refuse("map2d_cells_bwd", "the 2D-map head's backward scatters with float atomics and has no ordered form");
   STCAT_LAUNCH(map2d_cells_bwd_kernel, dim3(grid_for((long)b * ncells * D, 256)), dim3(256), 0, (hipStream_t)stream, pooled,
                cell_i, cell_j, ncells, dmap, dpooled, b, N, D);
   return launch_status();
@@ -1813,6 +1932,7 @@ int stcat_map2d_cells_bwd(const float* pooled, const int* cell_i, const int* cel
 
 int stcat_map2d_pool_bwd(const float* x, const float* dpooled, float* dx, int b, int T, int N, int D, void* stream) {
   if (b <= 0 || T <= 0 || N <= 0 || D <= 0) return fail("map2d_pool_bwd: bad shape");
+  if (g_deterministic) return det_refuse("map2d_pool_bwd", "the 2D-map head's backward scatters with float atomics and has no ordered form");
   STCAT_LAUNCH(map2d_pool_bwd_kernel, dim3(grid_for((long)b * N * D, 256)), dim3(256), 0, (hipStream_t)stream, x, dpooled, dx,
                b, T, N, D);
   return launch_status();
@@ -1882,6 +2002,7 @@ const stcat_plan::FnEntry g_plan_fns[] = {
     STCAT_PLAN_FN(stcat_map2d_pool_bwd),
     STCAT_PLAN_FN(stcat_rowscale),
     STCAT_PLAN_FN(stcat_grad_sqnorm),
+    STCAT_PLAN_FN(stcat_grad_sqnorm_ws),
     STCAT_PLAN_FN(stcat_grad_clip_scale),
     STCAT_PLAN_FN(stcat_ema_update),
     STCAT_PLAN_FN(stcat_temporal_map_argmax),

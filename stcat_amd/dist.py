@@ -253,6 +253,17 @@ class GradBucketReducer:
 
     def _launch(self, b):
         if self.comm:
+            # The bucket is reduced from the CURRENT stream, but early() filled its views from the stream of each
+            # delivering node (the forked time decoder and the weight-gradient stream deliver beside the main chain):
+            # order the collective behind every one of them, or it reads a view whose copy is still queued elsewhere.
+            if self._early_stream and b["flat"].is_cuda:
+                cur = torch.cuda.current_stream(b["flat"].device)
+                waited = {cur.cuda_stream}
+                for _, p in b["params"]:
+                    st = self._early_stream.get(p)
+                    if st is not None and st.cuda_stream not in waited:
+                        waited.add(st.cuda_stream)
+                        cur.wait_stream(st)
             srcs, dsts = [], []
             grads = b.get("static") if self.deferred else [p.grad for _, p in b["params"]]
             for (n, p), g, v in zip(b["params"], grads, b["views"]):

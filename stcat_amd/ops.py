@@ -1597,11 +1597,16 @@ def _wgrad_workspace(device, stream):
     capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
     if ws is None and WGRAD_WS_FLOATS > 0:
         if L.RECORDER is not None or capturing:
+            if L.is_deterministic():
+                raise L.StcatHipError("deterministic mode: the plane weight gradient needs its workspace, which a launch-plan "
+                                      "recording / graph capture cannot allocate; run one eager step on this stream first")
             return None       # (a recording / a hipGraph capture cannot allocate persistent memory: atomics path)
         ws = _WGRAD_WS[key] = torch.empty(WGRAD_WS_FLOATS if device.type == "cuda" else min(WGRAD_WS_FLOATS, 1 << 22),
                                           device=device, dtype=_f32)
     rec = L.RECORDER
-    if ws is not None and rec is not None and device.type == "cuda" and rec.slots.get(key[1]) == 0:
+    if (ws is not None and rec is not None and device.type == "cuda" and rec.slots.get(key[1]) == 0
+            and key not in rec.__dict__.setdefault("wgrad_ws_checked", set())):    # once per recorder, not per launch
+        rec.wgrad_ws_checked.add(key)
         #  the workspace is keyed by the stream the launch was RECORDED on, but a replay maps slot 0 to
         # whatever stream is current then: replayed elsewhere, the plan would share this buffer with eager launches of
         # the recorded stream, unordered.  Refuse such a replay instead of racing.
@@ -1617,6 +1622,8 @@ def _wgrad_workspace(device, stream):
 
 def free_wgrad_workspaces() -> None:
     """drop the per-stream workspaces (plans.clear(): the plans that baked their addresses are gone)"""
+    if _WGRAD_WS and any(ws.is_cuda for ws in _WGRAD_WS.values()):
+        torch.cuda.synchronize()     # launches still queued on their streams may be reading / writing them
     _WGRAD_WS.clear()
 
 

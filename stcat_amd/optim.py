@@ -33,6 +33,7 @@ class _TensorTable:
         self.key = None
         self.table = self.chunk_tensor = self.chunk_off = None
         self.n_chunks = 0
+        self.partials = None
         self.entry = L.load().stcat_optim_table_entry_bytes()
         assert self.entry == 56, self.entry
 
@@ -56,6 +57,8 @@ class _TensorTable:
         self.chunk_tensor = torch.tensor(ct, dtype=torch.int32).to(self.device)
         self.chunk_off = torch.tensor(co, dtype=torch.int64).to(self.device)
         self.n_chunks = len(ct)
+        # one partial sum per chunk: the workspace of the ordered squared norm (stcat_grad_sqnorm_ws, deterministic mode)
+        self.partials = torch.empty(max(self.n_chunks, 1), dtype=torch.float32, device=self.device)
 
 
 def _dense(t: torch.Tensor) -> bool:
@@ -70,6 +73,16 @@ def _same_layout(a: torch.Tensor, b: torch.Tensor) -> bool:
 
 def _ptr(t: Optional[torch.Tensor]) -> int:
     return 0 if t is None else t.data_ptr()
+
+
+def _grad_sqnorm(t: _TensorTable, sq: torch.Tensor, stream) -> None:
+    """sq[0] = sum |g|^2 over the table; in deterministic mode through the table's per-chunk workspace (ordered sum)"""
+    if L.is_deterministic():
+        L.call("stcat_grad_sqnorm_ws", t.table.data_ptr(), t.chunk_tensor.data_ptr(), t.chunk_off.data_ptr(),
+               t.n_chunks, CHUNK, sq.data_ptr(), t.partials.data_ptr(), t.partials.numel(), stream)
+    else:
+        L.call("stcat_grad_sqnorm", t.table.data_ptr(), t.chunk_tensor.data_ptr(), t.chunk_off.data_ptr(),
+               t.n_chunks, CHUNK, sq.data_ptr(), stream)
 
 
 class AdamW:
@@ -159,8 +172,7 @@ class AdamW:
         ops.WEIGHT_EPOCH += 1  # parameters change below through raw pointers: derived copies (weight planes) are stale
         sq = None
         if max_grad_norm and max_grad_norm > 0:
-            L.call("stcat_grad_sqnorm", t.table.data_ptr(), t.chunk_tensor.data_ptr(), t.chunk_off.data_ptr(),
-                   t.n_chunks, CHUNK, self._sq.data_ptr(), stream)
+            _grad_sqnorm(t, self._sq, stream)
             sq = self._sq
         lr = np.array([g["lr"] for g in self.param_groups], dtype=np.float32)
         wd = np.array([g["weight_decay"] for g in self.param_groups], dtype=np.float32)
@@ -272,8 +284,7 @@ def clip_grad_norm_(parameters: Iterable[torch.Tensor], max_norm: float) -> torc
     tab.update([(0, p.grad.data_ptr(), 0, 0, 0, p.grad.numel(), 0) for p in ps])
     sq = torch.zeros(1, device=dev)
     st = L.stream_of(ps[0])
-    L.call("stcat_grad_sqnorm", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(),
-           tab.n_chunks, CHUNK, sq.data_ptr(), st)
+    _grad_sqnorm(tab, sq, st)
     # g *= min(1, max_norm / (norm + 1e-6)) with the coefficient computed on the device: no host sync
     L.call("stcat_grad_clip_scale", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(),
            tab.n_chunks, CHUNK, sq.data_ptr(), float(max_norm), st)
