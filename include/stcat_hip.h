@@ -326,8 +326,12 @@ int stcat_mha_self_bwd_lse(const float* q, const float* k, const float* v, const
  * mma mode: two bf16 planes per operand and three products (modes bf16x3 / bf16x6 / bf16x3p), or — mode bf16x6p,
  * round 6 — THREE planes per operand (their sum is the fp32 value) and the six cross terms of the plane GEMMs, also
  * for the probabilities and dS that feed the second contraction.  stcat_mha_bs_bwd recomputes the probabilities from
- * q, k and lse (S <= 256): ONE launch for two planes; for three planes two launches (dQ with K / V planes in LDS, dK / dV
- * with Q / dO planes in LDS: all four as three planes would be 172 KB at S = 224).
+ * q, k and lse.  S <= 256: ONE launch for two planes; for three planes two launches (dQ with K / V planes in LDS, dK / dV
+ * with Q / dO planes in LDS: all four as three planes would be 172 KB at S = 224), one workgroup per (batch, head).
+ * S > 256 (any length): the same two launches in a streaming form for either plane count — grid (B*H, ceil(tiles / 4)),
+ * one 32-row tile per wave held in registers, the other operand through LDS in 128-row super-chunks (32.5 / 48.5 KB,
+ * independent of S).  No atomics and no workspace in any form: every dq / dk / dv element has one writer and one
+ * summation order (bit-reproducible; valid in deterministic mode as it is).
  * Replaces nn.MultiheadAttention's core in modal_encoder.py:161-168, 180-185, 228-242 and query_decoder.py:341. */
 int stcat_mha_bs_fwd(const float* q, const float* k, const float* v, const unsigned char* kpm, float* o, float* lse,
                      int B, int H, int S, int ldq, int ldk, int ldv, int ldo, float scale, float drop_p, long drop_seed,

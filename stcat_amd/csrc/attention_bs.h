@@ -598,3 +598,182 @@ __global__ void __launch_bounds__(64 * NW) mha_bs_bwd_dkv_kernel(AttnBsParams p,
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------
+// backward for rows longer than 256 tokens: the two-launch recomputing pair above with the OTHER operand streamed.
+// A wave still owns one 32-row tile — its rows in registers as plane fragments, its gradient tile accumulated in registers
+// over the whole row — but the tiles it contracts with pass through LDS in super-chunks of STCAT_ABS_LONG_SC rows, so LDS
+// no longer grows with S: 2 NP planes of 128 rows = 33 KB (NP = 2) / 49 KB (NP = 3) per workgroup of NW = 4 waves.  The
+// kernels hold 184 - 250 registers per lane, so two workgroups share a CU; the forward's 256-row super-chunk (97 KB at
+// NP = 3) would leave one (profiles/mha_bs_long_rows.log).
+//   dQ kernel:    grid (B*H, ceil(query tiles / NW)).  K, V stream; Q (pre-scaled), dO rows and delta_q in registers.
+//   dK/dV kernel: grid (B*H, ceil(key tiles / NW)).  Q (pre-scaled), dO stream with their lse and delta; K, V rows in registers.
+// Every dQ / dK / dV element has one writer and one summation order: no atomics, no workspace, bit-reproducible.  A
+// fully padded chunk contributes exact zeros (exp(-inf) = 0; no running maximum to go wrong); rows >= S are staged as zeros.
+// ---------------------------------------------------------------------------------------------------
+#define STCAT_ABS_LONG_SC 128
+#define STCAT_ABS_LONG_NW 4
+
+template <int NW, int NP>
+__global__ void __launch_bounds__(64 * NW) mha_bs_bwd_dq_long_kernel(AttnBsParams p, const float* Og) {
+  p.drop = stcat_drop_resolve(p.drop);
+  constexpr int SC = STCAT_ABS_LONG_SC, PLANE = SC * STCAT_ABS_ROWB;
+  STCAT_DYN_SHARED(char, smem);
+  char* Kp = smem; char* Vp = smem + NP * PLANE;
+  float* kb = reinterpret_cast<float*>(smem + 2 * NP * PLANE);
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
+  const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
+  const int SP = ((p.S + 31) / 32) * 32;
+  const int q0 = (blockIdx.y * NW + wave) * 32;   // a wave whose tile starts beyond S only helps staging
+  const int q = q0 + l31;
+  const float* Kg = p.K + (long)b * p.S * p.ldk + h * 32;
+  const float* Vg = p.V + (long)b * p.S * p.ldv + h * 32;
+  AbsFrag<NP> qf[2], gf[2];
+  stcat_abs_rowregs<NP>(p.Q + (long)b * p.S * p.ldq + h * 32, p.ldq, q, p.S, hi, p.scale, qf);
+  stcat_abs_rowregs<NP>(p.dO + (long)b * p.S * p.ldo + h * 32, p.ldo, q, p.S, hi, 1.f, gf);
+  float dq_ = 0.f, lq = 0.f;
+  if (q < p.S) {
+    const float* g = p.dO + ((long)b * p.S + q) * p.ldo + h * 32 + 16 * hi;     // (half a row per lane of the pair)
+    const float* og = Og + ((long)b * p.S + q) * p.ldo + h * 32 + 16 * hi;
+    STCAT_UNROLL
+    for (int c = 0; c < 4; ++c) {
+      const float4 a = stcat_ld4(g + 4 * c), o4 = stcat_ld4(og + 4 * c);
+      dq_ += a.x * o4.x + a.y * o4.y + a.z * o4.z + a.w * o4.w;
+    }
+    lq = p.lse[(long)blockIdx.x * p.S + q];
+  }
+  dq_ += __shfl_xor(dq_, 32);
+  f32x16 dq;
+  STCAT_UNROLL
+  for (int r = 0; r < 16; ++r) dq[r] = 0.f;
+  for (int sc0 = 0; sc0 < p.S; sc0 += SC) {
+    if (sc0) __syncthreads();  // everybody is done with the previous super-chunk
+    stcat_abs_stage_n<SC, NP>(Kg, p.ldk, sc0, p.S, Kp, PLANE, t, 64 * NW, 1.f);
+    stcat_abs_stage_n<SC, NP>(Vg, p.ldv, sc0, p.S, Vp, PLANE, t, 64 * NW, 1.f);
+    for (int i = t; i < SC; i += 64 * NW)
+      kb[i] = (sc0 + i < p.S && !(p.kpm && p.kpm[(long)b * p.S + sc0 + i])) ? 0.f : STCAT_NEG_INF;
+    __syncthreads();
+    if (q0 >= p.S) continue;   // wave-uniform; the barriers above are reached by every wave
+    for (int k0 = 0; k0 < SC && sc0 + k0 < p.S; k0 += 32) {
+      f32x16 s_, dp;
+      STCAT_UNROLL
+      for (int r = 0; r < 16; ++r) { s_[r] = 0.f; dp[r] = 0.f; }
+      STCAT_UNROLL
+      for (int s = 0; s < 2; ++s) {
+        AbsFrag<NP> kf, vf;
+        stcat_abs_rowfrag_n<NP>(Kp, PLANE, k0 + l31, 2 * s + hi, kf);
+        stcat_abs_rowfrag_n<NP>(Vp, PLANE, k0 + l31, 2 * s + hi, vf);
+        stcat_abs_mma<NP>(s_, kf, qf[s]);
+        stcat_abs_mma<NP>(dp, vf, gf[s]);
+      }
+      STCAT_UNROLL
+      for (int r = 0; r < 16; ++r) {
+        const int kl = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const float pr = (q < p.S) ? __expf(s_[r] + kb[kl] - lq) : 0.f;   // masked / padded keys: exp(-inf) = 0
+        float dpv = dp[r];
+        if (p.drop.thresh) dpv *= stcat_drop_mul(p.drop, ((unsigned long long)blockIdx.x * SP + sc0 + kl) * SP + q);
+        s_[r] = pr * (dpv - dq_);                                         // dS (the scale rides in Q / below)
+      }
+      STCAT_UNROLL
+      for (int j = 0; j < 2; ++j) {
+        AbsFrag<NP> df, ktf;
+        stcat_abs_split_acc<NP>(s_, j, df);
+        stcat_abs_trfrag_n<NP>(Kp, PLANE, k0 + 16 * j, lane, ktf);
+        stcat_abs_mma<NP>(dq, ktf, df);
+      }
+    }
+  }
+  if (q < p.S) {
+    float* g = p.dQ + ((long)b * p.S + q) * p.ldg + h * 32 + 4 * hi;
+    STCAT_UNROLL
+    for (int c = 0; c < 4; ++c)
+      stcat_st4(g + 8 * c, make_float4(dq[4 * c] * p.scale, dq[4 * c + 1] * p.scale, dq[4 * c + 2] * p.scale,
+                                       dq[4 * c + 3] * p.scale));
+  }
+}
+
+template <int NW, int NP>
+__global__ void __launch_bounds__(64 * NW) mha_bs_bwd_dkv_long_kernel(AttnBsParams p, const float* Og) {
+  p.drop = stcat_drop_resolve(p.drop);
+  constexpr int SC = STCAT_ABS_LONG_SC, PLANE = SC * STCAT_ABS_ROWB;
+  STCAT_DYN_SHARED(char, smem);
+  char* Qp = smem; char* Gp = smem + NP * PLANE;
+  float* lse = reinterpret_cast<float*>(smem + 2 * NP * PLANE);
+  float* dlt = lse + SC;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, hi = lane >> 5;
+  const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
+  const int SP = ((p.S + 31) / 32) * 32;
+  const int key0 = (blockIdx.y * NW + wave) * 32;   // a wave whose tile starts beyond S only helps staging
+  const int key = key0 + l31;
+  const float* Qg = p.Q + (long)b * p.S * p.ldq + h * 32;
+  const float* Gg = p.dO + (long)b * p.S * p.ldo + h * 32;
+  AbsFrag<NP> kf[2], vf[2];
+  stcat_abs_rowregs<NP>(p.K + (long)b * p.S * p.ldk + h * 32, p.ldk, key, p.S, hi, 1.f, kf);
+  stcat_abs_rowregs<NP>(p.V + (long)b * p.S * p.ldv + h * 32, p.ldv, key, p.S, hi, 1.f, vf);
+  const float kbias = (key < p.S && !(p.kpm && p.kpm[(long)b * p.S + key])) ? 0.f : STCAT_NEG_INF;
+  f32x16 dv, dk;
+  STCAT_UNROLL
+  for (int r = 0; r < 16; ++r) { dv[r] = 0.f; dk[r] = 0.f; }
+  for (int sc0 = 0; sc0 < p.S; sc0 += SC) {
+    if (sc0) __syncthreads();  // everybody is done with the previous super-chunk
+    stcat_abs_stage_n<SC, NP>(Qg, p.ldq, sc0, p.S, Qp, PLANE, t, 64 * NW, p.scale);
+    stcat_abs_stage_n<SC, NP>(Gg, p.ldo, sc0, p.S, Gp, PLANE, t, 64 * NW, 1.f);
+    for (int i = t; i < SC; i += 64 * NW) {
+      float d = 0.f, ls = 0.f;
+      if (sc0 + i < p.S) {
+        const float* g = Gg + (long)(sc0 + i) * p.ldo;
+        const float* og = Og + ((long)b * p.S + sc0 + i) * p.ldo + h * 32;
+        STCAT_UNROLL
+        for (int c = 0; c < 8; ++c) {
+          const float4 a = stcat_ld4(g + 4 * c), o4 = stcat_ld4(og + 4 * c);
+          d += a.x * o4.x + a.y * o4.y + a.z * o4.z + a.w * o4.w;
+        }
+        ls = p.lse[(long)blockIdx.x * p.S + sc0 + i];
+      }
+      dlt[i] = d;
+      lse[i] = ls;
+    }
+    __syncthreads();
+    if (key0 >= p.S) continue;   // wave-uniform; the barriers above are reached by every wave
+    for (int q0 = 0; q0 < SC && sc0 + q0 < p.S; q0 += 32) {
+      f32x16 s_, dp;
+      STCAT_UNROLL
+      for (int r = 0; r < 16; ++r) { s_[r] = 0.f; dp[r] = 0.f; }
+      STCAT_UNROLL
+      for (int s = 0; s < 2; ++s) {
+        AbsFrag<NP> af, bf;
+        stcat_abs_rowfrag_n<NP>(Qp, PLANE, q0 + l31, 2 * s + hi, af);
+        stcat_abs_rowfrag_n<NP>(Gp, PLANE, q0 + l31, 2 * s + hi, bf);
+        stcat_abs_mma<NP>(s_, af, kf[s]);   // S[q][key]
+        stcat_abs_mma<NP>(dp, bf, vf[s]);   // dP[q][key] = dO_q . V_key
+      }
+      STCAT_UNROLL
+      for (int r = 0; r < 16; ++r) {
+        const int ql = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi, qq = sc0 + ql;
+        const float pr = (qq < p.S) ? __expf(s_[r] + kbias - lse[ql]) : 0.f;
+        const float dm = p.drop.thresh ? stcat_drop_mul(p.drop, ((unsigned long long)blockIdx.x * SP + key) * SP + qq) : 1.f;
+        s_[r] = pr * (dp[r] * dm - dlt[ql]);   // dS[q][key]
+        dp[r] = pr * dm;                        // P' (dropped probabilities) for dV
+      }
+      STCAT_UNROLL
+      for (int j = 0; j < 2; ++j) {
+        AbsFrag<NP> pf, df, gtf, qtf;
+        stcat_abs_split_acc<NP>(dp, j, pf);
+        stcat_abs_split_acc<NP>(s_, j, df);
+        stcat_abs_trfrag_n<NP>(Gp, PLANE, q0 + 16 * j, lane, gtf);
+        stcat_abs_trfrag_n<NP>(Qp, PLANE, q0 + 16 * j, lane, qtf);
+        stcat_abs_mma<NP>(dv, gtf, pf);   // dV^T[d][key] += dO^T[d][q] P'[q][key]
+        stcat_abs_mma<NP>(dk, qtf, df);   // dK^T[d][key] += (scale Q)^T[d][q] dS[q][key]
+      }
+    }
+  }
+  if (key < p.S) {
+    float* gv = p.dV + ((long)b * p.S + key) * p.ldgv + h * 32 + 4 * hi;
+    float* gk = p.dK + ((long)b * p.S + key) * p.ldg + h * 32 + 4 * hi;
+    STCAT_UNROLL
+    for (int c = 0; c < 4; ++c) {
+      stcat_st4(gv + 8 * c, make_float4(dv[4 * c], dv[4 * c + 1], dv[4 * c + 2], dv[4 * c + 3]));
+      stcat_st4(gk + 8 * c, make_float4(dk[4 * c], dk[4 * c + 1], dk[4 * c + 2], dk[4 * c + 3]));
+    }
+  }
+}

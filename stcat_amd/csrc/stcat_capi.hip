@@ -1877,7 +1877,6 @@ int stcat_mha_bs_bwd(const float* q, const float* k, const float* v, const unsig
                      int ldk, int ldv, int ldo, int ldg, int ldgv, float scale, float drop_p, long drop_seed,
                      long drop_offset, const long* drop_base, void* stream) {
   if (S <= 0 || B <= 0 || H <= 0) return fail("mha_bs_bwd: bad shape");
-  if (S > 256) return fail("mha_bs_bwd: S=%d exceeds 256 tokens (training on longer token rows is not built yet)", S);
   if ((ldq | ldk | ldv | ldo | ldg | ldgv) % 4 != 0) return fail("mha_bs_bwd: ld %% 4 != 0");
   AttnBsParams p = {};
   p.Q = q; p.K = k; p.V = v; p.lse = const_cast<float*>(lse); p.kpm = kpm; p.dO = dout; p.dQ = dq; p.dK = dk; p.dV = dv;
@@ -1885,6 +1884,26 @@ int stcat_mha_bs_bwd(const float* q, const float* k, const float* v, const unsig
   p.drop = stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base);
   const int nw = cdiv(S, 32);
   hipStream_t st = (hipStream_t)stream;
+  if (S > 256) {
+    // rows longer than 256 tokens: the streaming pair (one 32-row tile per wave, the other operand through LDS in
+    // super-chunks), in either plane count; LDS does not depend on S
+    constexpr int NW = STCAT_ABS_LONG_NW;
+    const dim3 grid(B * H, cdiv(nw, NW));
+    if (mha_bs_planes() == 3) {
+      const int lds = 6 * STCAT_ABS_LONG_SC * 64 + 2 * STCAT_ABS_LONG_SC * 4;
+      if (int rc = pl_prepare(mha_bs_bwd_dq_long_kernel<NW, 3>, lds)) return rc;
+      if (int rc = pl_prepare(mha_bs_bwd_dkv_long_kernel<NW, 3>, lds)) return rc;
+      STCAT_LAUNCH((mha_bs_bwd_dq_long_kernel<NW, 3>), grid, dim3(64 * NW), lds, st, p, out);
+      STCAT_LAUNCH((mha_bs_bwd_dkv_long_kernel<NW, 3>), grid, dim3(64 * NW), lds, st, p, out);
+    } else {
+      const int lds = 4 * STCAT_ABS_LONG_SC * 64 + 2 * STCAT_ABS_LONG_SC * 4;
+      if (int rc = pl_prepare(mha_bs_bwd_dq_long_kernel<NW, 2>, lds)) return rc;
+      if (int rc = pl_prepare(mha_bs_bwd_dkv_long_kernel<NW, 2>, lds)) return rc;
+      STCAT_LAUNCH((mha_bs_bwd_dq_long_kernel<NW, 2>), grid, dim3(64 * NW), lds, st, p, out);
+      STCAT_LAUNCH((mha_bs_bwd_dkv_long_kernel<NW, 2>), grid, dim3(64 * NW), lds, st, p, out);
+    }
+    return launch_status();
+  }
   if (mha_bs_planes() == 3) {
     // three planes of Q, K, V, dO do not fit one workgroup's LDS (172 KB at S = 224): dQ and dK / dV as two launches, each
     // with two operands as planes in LDS (86 KB) and its own tile's rows in registers

@@ -920,6 +920,9 @@ def _ld3(t: torch.Tensor) -> int:
 MHA_RECOMPUTE = bool(os.environ.get("STCAT_MHA_RECOMPUTE"))
 MHA_BS6_MIN_ROWS = int(os.environ.get("STCAT_MHA_BS6_MIN_ROWS", "128"))
 MHA_FP32_PIPE = bool(os.environ.get("STCAT_MHA_FP32_PIPE"))      # A/B switch: every mode's self-attention on the fp32-pipe kernels
+# OPT-IN: gradient-carrying rows of 257..512 tokens on the bf16-pipe kernels as well (no S x S stash, no dS scratch).  Rows
+# above 512 tokens always train there; the default of this band is unchanged (fp32 long-row kernels).
+MHA_BS_LONG = os.environ.get("STCAT_MHA_BS_LONG", "0") not in ("", "0")
 
 
 class MhaSelfFn(Function):
@@ -943,9 +946,11 @@ class MhaSelfFn(Function):
         # bf16-pipe kernels (csrc/attention_bs.h): online softmax, any S, only the row log-sum-exp is kept for backward.
         # The fp32-MFMA kernels remain for the exact-fp32 mode and for the one caller that consumes the head-mean
         # weights (the time decoder's self-attention, T queries).
-        # (mode bf16x6p is fp32-class end to end: its attention runs on the fp32 matrix pipe as well)
-        # rows longer than 256 tokens (non-square clips) train through the fp32 long-row kernels in every mode: the
-        # bf16-pipe backward keeps a whole row's tiles in LDS and is built for S <= 256
+        # Rows longer than 256 tokens (non-square clips) with gradients: the bf16-pipe backward has a streaming form for them
+        # (mha_bs_bwd_*_long_kernel: one 32-row tile per wave, the other operand through LDS in 128-row super-chunks; only
+        # the row log-sum-exp is kept).  Above 512 tokens it is the only training route — the fp32-pipe kernels stop there.
+        # For 256 < S <= 512 the DEFAULT stays the fp32 long-row kernels (S x S probability stash + a same-sized dS scratch:
+        # 2 x 210 MB per spatial layer at T = 64, S = 310); MHA_BS_LONG sends that band to the bf16-pipe kernels too.
         # (round 6: mode bf16x6p runs here too — three planes per operand, six products: csrc/attention_bs.h, NP = 3; the
         #  frozen experimental mode f16x3p keeps the fp32-pipe kernels)
         # In bf16x6p only rows longer than 128 tokens take the six-product kernels (the encoder's spatial layers: 207 at C3):
@@ -954,9 +959,17 @@ class MhaSelfFn(Function):
         # 256 staged rows and 97 KB of LDS per workgroup do not pay on two or three tiles) — and those launches sit on the
         # step's latency-bound chains.
         mode = L.get_mma_mode()
+        grads = any(ctx.needs_input_grad[:3])
         ctx.bs = ((not need_weights) and mode not in ("f32", "f16x3p") and not MHA_FP32_PIPE
                   and (mode != "bf16x6p" or S > MHA_BS6_MIN_ROWS)
-                  and (S <= 256 or not any(ctx.needs_input_grad[:3])))
+                  and (S <= 256 or S > 512 or MHA_BS_LONG or not grads))
+        if not ctx.bs and S > 512:
+            why = ("the head-mean attention weights are wanted" if need_weights else
+                   f"mma mode {mode!r}" if mode in ("f32", "f16x3p") else
+                   "STCAT_MHA_FP32_PIPE is set" if MHA_FP32_PIPE else
+                   f"MHA_BS6_MIN_ROWS = {MHA_BS6_MIN_ROWS} keeps mode 'bf16x6p' off the bf16 pipe up to that row length")
+            raise ValueError(f"mha_self: {S} tokens per row, {why}: this call runs on the fp32-pipe attention kernels, which "
+                             "stop at 512 tokens per row; longer rows need mode bf16x3, bf16x3p or bf16x6p and no weights")
         if ctx.bs:
             keep = any(ctx.needs_input_grad[:3])
             lse = _empty(v, B, H, S) if keep else None

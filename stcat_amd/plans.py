@@ -463,7 +463,7 @@ def _global_sig(dev):
     ds = ops._dropout_stream
     base = ds.base(dev).data_ptr() if dev in ds._base else 0
     return (L.get_mma_mode(), L.is_deterministic(), STATIC_EPOCH, ds.offset, ds.seed, base, id(ops.GRAD_SINK), ops.FORK_ENABLED,
-            ops.WGRAD_STREAM_ENABLED)
+            ops.WGRAD_STREAM_ENABLED, ops.MHA_BS_LONG)
 
 
 def _record(dev, ext, pool, body):

@@ -332,6 +332,14 @@ def sample_indices(name: str, numel: int, k: int = 1024) -> np.ndarray:
     return idx
 
 
+def thinned_positions(n: int, k: int) -> np.ndarray:
+    """Which of the n elements of a stored gradient sample a fixture thinned to at most k per tensor keeps
+    (tools/thin_model_fixture.py): all of them, or k evenly spaced ones.  Sorted, int64."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.linspace(0, n - 1, k).astype(np.int64)
+
+
 # model-level parity cases: name -> (T, resolution or (H, W), text tokens, padding, with backward).  The fixtures
 # tests/golden/model_<name>.npz hold what the imported reference computes for them (tests/golden/make_golden.py).
 MODEL_CASES = {
@@ -342,6 +350,8 @@ MODEL_CASES = {
     "SQ8_ragged": (8, 224, 10, "ragged", True),
     "NS8": (8, (405, 720), 10, None, True),
     "NS8_ragged": (8, (405, 720), 10, "ragged", True),
+    # more than 512 tokens per frame (22 x 23 map + text + cls = 517): above the fp32-pipe attention kernels' limit
+    "HR8": (8, (704, 736), 10, None, True),
     # train-mode fixtures (round 6): the same clips, expected values from the oracle fed with the recorded dropout stream
     # of the benchmark's own step (tests/golden/make_golden.py train ...; files model_<case>.npz)
     "C1_train": (8, 224, 10, None, True),
