@@ -17,23 +17,18 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
+import os
+
 from . import ops, plans
 from .misc import NestedTensor
 
-import os
-
 BLOCKS = (3, 4, 23, 3)
-# the plane-format forward as N frame-range chains on N streams (default 2; 1 = off)
-FORWARD_CHAINS = 1 if os.environ.get("STCAT_NO_FORWARD_CHAINS") else int(os.environ.get("STCAT_FORWARD_CHAINS", "2"))
-# the same for the data-gradient chain of the backward pass: measured neutral next to the weight-gradient stream
-# (86.9 vs 86.9 ms per C3 step), so opt-in
-BACKWARD_CHAINS = bool(os.environ.get("STCAT_BACKWARD_CHAINS"))
-COARSE_ADD = not os.environ.get("STCAT_NO_COARSE_ADD")   # downsample-branch gradient added from its own grid (round 5)
+# the plane-format forward as N frame-range chains on N streams (1 = off; graph.py turns them off around a hipGraph capture).
+# The same split of the backward pass's data-gradient chain measured neutral next to the weight-gradient stream (86.9 vs
+# 86.9 ms per C3 step) and is gone.
+FORWARD_CHAINS = 2
 # round 6: the next clip's frozen prefix (stem + max-pool + layer1) under the current step's grounding section
 PREFIX_PIPELINE = not os.environ.get("STCAT_NO_PREFIX_PIPELINE")
-PREFIX_STREAM = int(os.environ.get("STCAT_PREFIX_STREAM", "2"))     # index into ops.side_stream (2 = the spare queue)
-PREFIX_PRIO = int(os.environ.get("STCAT_PREFIX_PRIO", "0"))         # 0 = a measured-concurrent default-priority side stream; 1 = least priority
-PREFIX_CUS = int(os.environ.get("STCAT_PREFIX_CUS", "0"))           # > 0: the prefix stream is masked to this many CUs
 # the prefix blocks' convs in pieces of this many frames (0 = the forward chains' own ranges).  Default "auto": 4 frames on a
 # single GPU, 0 under a live gradient exchange — measured both ways on one box (profiles/r06_prefix_pipeline.log): pieces of
 # 4 gain 0.65 ms per step without a process group and LOSE 0.8 ms with one (the longer-lived prefix then also shares the
@@ -46,8 +41,6 @@ def _prefix_range() -> int:
         return int(_PREFIX_RANGE_ENV)
     sink = ops.GRAD_SINK
     return 0 if (sink is not None and getattr(sink, "comm", False)) else 4
-PREFIX_EAGER = bool(os.environ.get("STCAT_PREFIX_EAGER"))           # the staged prefix launch by launch (no launch plan)
-PREFIX_AT = os.environ.get("STCAT_PREFIX_AT", "decoder")             # "decoder": queued at the query decoder's entry; "backbone"
 
 
 def _chain_streams(dev, k):
@@ -58,6 +51,8 @@ def _chain_streams(dev, k):
     group, whose stream is the fifth, the second forward chain landed on the main stream's queue and the forward lost
     its overlap, +3.5 ms per step; profiles/r03_hw_queues.log)."""
     return [ops.side_stream(dev, i) for i in range(k - 1)]
+
+
 PLANES = (64, 128, 256, 512)
 
 
@@ -152,67 +147,20 @@ _PREFIX_LANES = {}
 
 
 def _prefix_lane(dev):
-    """the stream the next clip's prefix runs on.  Default: the spare one of the package's measured-concurrent side streams
-    (ops.side_stream(dev, PREFIX_STREAM): main, forward chain / time decoder, weight gradients and this one fill the four
+    """the stream the next clip's prefix runs on: the spare one of the package's measured-concurrent side streams
+    (ops.side_stream(dev, 2): main, forward chain / time decoder, weight gradients and this one fill the four
     hardware queues HIP gives a process).  Measured and rejected (profiles/r06_prefix_pipeline.log, same box, ms per C3
-    step; off = 77.3): a stream of the device's least priority (STCAT_PREFIX_PRIO=1) 94.8, a stream masked to 192 / 128 /
-    64 compute units (STCAT_PREFIX_CUS=n) 111-127 — a stream created beside torch's pool lands on a hardware queue that
-    one of the step's streams already uses and the two serialise (the node timeline shows the decoders waiting for the
-    whole prefix)."""
+    step; off = 77.3): a stream of the device's least priority 94.8, a stream masked to 192 / 128 / 64 compute units
+    111-127 — a stream created beside torch's pool lands on a hardware queue that one of the step's streams already uses
+    and the two serialise (the node timeline shows the decoders waiting for the whole prefix)."""
     key = str(dev)
     st = _PREFIX_LANES.get(key)
     if st is None:
-        if PREFIX_CUS > 0 or PREFIX_PRIO != 0:
-            st = _probed_lane(dev)
-        if st is None:
-            st = ops.side_stream(dev, PREFIX_STREAM)
-        _PREFIX_LANES[key] = st
+        st = _PREFIX_LANES[key] = ops.side_stream(dev, 2)
     return st
 
 
-def _probed_lane(dev):
-    """A stream made by stcat_stream_create (CU mask / priority) that does NOT share a hardware queue with the main stream,
-    the forward-chain / time-decoder stream or the weight-gradient stream.  HIP hands new streams to its four hardware
-    queues round-robin, and the step's four streams occupy all of them: a fifth stream serialises with whichever one it
-    lands on (measured: 94-127 ms per step).  So several candidates are created and each is timed against the three busy
-    streams with the 500 us spin kernel, as ops._pick_streams does; the first one that runs beside all three is kept — it
-    shares its queue with the spare side stream, which the prefix then no longer uses.  None if no candidate qualifies."""
-    import ctypes
-    import time
-    lib = ops.L.load()
-    busy = [torch.cuda.current_stream(dev), ops.side_stream(dev, 0), ops.side_stream(dev, 1)]
-
-    def run_ms(streams):
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for s_ in streams:
-            if lib.stcat_spin(500, s_.cuda_stream) != 0:
-                raise ops.L.StcatHipError("stcat_spin failed")
-        torch.cuda.synchronize(dev)
-        return (time.perf_counter() - t0) * 1e3
-
-    single = min(run_ms(busy[:1]) for _ in range(3))
-    report = []
-    for _ in range(8):
-        out = ctypes.c_void_p()
-        with torch.cuda.device(dev):
-            rc = lib.stcat_stream_create(PREFIX_PRIO, PREFIX_CUS, ctypes.byref(out))
-        if rc != 0 or not out.value:
-            raise ops.L.StcatHipError("stcat_stream_create failed: " + lib.stcat_last_error().decode())
-        cand = torch.cuda.ExternalStream(out.value, device=dev)
-        run_ms([cand])
-        pair = [min(run_ms([b, cand]), run_ms([b, cand])) for b in busy]
-        report.append([round(x, 3) for x in pair])
-        if all(x < 1.5 * single for x in pair):
-            PREFIX_LANE_REPORT[str(dev)] = {"spin_ms": round(single, 3), "pairs_ms": report, "picked": len(report) - 1}
-            return cand
-        torch.cuda.synchronize(dev)
-        lib.stcat_stream_destroy(out)
-    PREFIX_LANE_REPORT[str(dev)] = {"spin_ms": round(single, 3), "pairs_ms": report, "picked": None}
-    return None
-
-
-PREFIX_LANE_REPORT = {}
+PREFIX_LANE_REPORT = {}     # (bench.py reports it; filled only by a lane probe, and the default lane needs none)
 
 
 def _prefix_blocks(body):
@@ -530,16 +478,7 @@ class _BackboneFnPl(Function):
         sink = ops.GRAD_SINK
         delivered = set()
 
-        # The data-gradient chain as two half-clip chains on two streams (BACKWARD_CHAINS), like the forward pass: every
-        # data gradient is issued once per half into one whole-batch tensor; the weight gradients stay whole-batch
-        # launches on the weight-gradient stream, ordered behind both halves.
-        n_all = tape[-1][1].shape[0]
-        fork = ops.fork_stream(dy) if (BACKWARD_CHAINS and n_all >= 8 and dy.is_cuda) else None
-        chains = [(0, n_all // 2), (n_all // 2, n_all)] if (fork is not None and fork.active) else None
-
         def wgrad(param, g, xin, wshape, stride, pad, row_scale=None):
-            if chains is not None:      # g's second half is written by the second chain
-                ops._wait_stream(wg.side if wg.active else fork.main, fork.side)
             # data-parallel run: accumulate straight into the parameter's slot of its flat gradient bucket
             tgt = sink.grad_target(param) if sink is not None else None
             with wg:
@@ -547,53 +486,11 @@ class _BackboneFnPl(Function):
                                                          out=tgt.permute(0, 2, 3, 1) if tgt is not None else None)
             wg.keep(g, xin)
 
-        def dgrad(g, wt_, in_shape, k, stride, pad, add=None, out=None, mask_y=None, mask_scale=None):
-            if chains is None:
-                return ops.pl_conv_dgrad_raw(g, wt_, in_shape, k, stride, pad, add=add, out=out, mask_y=mask_y,
-                                             mask_scale=mask_scale)
-            dx = out
-            if dx is None:
-                dx = ops.Planes.empty(g.t, *in_shape)
-                dx.t.record_stream(fork.side)
-                if ops.L.RECORDER is not None:
-                    ops.L.RECORDER.keep.append(dx.t)
-            for ci, (a, b) in enumerate(chains):
-                kw = dict(add=add.frames(a, b) if add is not None else None, out=dx.frames(a, b),
-                          mask_y=mask_y.frames(a, b) if mask_y is not None else None, mask_scale=mask_scale)
-                shp = (b - a,) + tuple(in_shape[1:])
-                if ci == 0:
-                    ops.pl_conv_dgrad_raw(g.frames(a, b), wt_, shp, k, stride, pad, **kw)
-                else:
-                    with torch.cuda.stream(fork.side):
-                        ops.pl_conv_dgrad_raw(g.frames(a, b), wt_, shp, k, stride, pad, **kw)
-            return dx
-
-        def dgrad_cadd(g, wt_, in_shape, addc, add_stride, mask_y):
-            if chains is None:
-                return ops.pl_conv_dgrad_cadd_raw(g, wt_, in_shape, addc, add_stride, mask_y=mask_y)
-            dx = ops.Planes.empty(g.t, *in_shape)
-            dx.t.record_stream(fork.side)
-            if ops.L.RECORDER is not None:
-                ops.L.RECORDER.keep.append(dx.t)
-            for ci, (a, b) in enumerate(chains):
-                shp = (b - a,) + tuple(in_shape[1:])
-                args = (g.frames(a, b), wt_, shp, addc.frames(a, b), add_stride)
-                kw = dict(mask_y=mask_y.frames(a, b), out=dx.frames(a, b))
-                if ci == 0:
-                    ops.pl_conv_dgrad_cadd_raw(*args, **kw)
-                else:
-                    with torch.cuda.stream(fork.side):
-                        ops.pl_conv_dgrad_cadd_raw(*args, **kw)
-            return dx
+        dgrad, dgrad_cadd = ops.pl_conv_dgrad_raw, ops.pl_conv_dgrad_cadd_raw
 
         blk, x, o1, o2, y, _, (s1, s2, s3, sd) = tape[-1]
         # top of the stack (y is the fp32 layer4 output): dz = dy * [y > 0] as planes
         _, dz = ops.pl_act_bwd_raw(dy.contiguous(), y, None, want_g=False, want_res=True, relu=True)
-        if chains is not None:
-            dz.t.record_stream(fork.side)
-            if ops.L.RECORDER is not None:
-                ops.L.RECORDER.keep.append(dz.t)
-            ops._wait_stream(fork.side, fork.main)
         for idx in range(len(tape) - 1, -1, -1):
             blk, x, o1, o2, y, (w1, w2, w3, wd), (s1, s2, s3, sd) = tape[idx]
             need_dx = idx > 0  # below the first trainable block everything is frozen (backbone.py:78-85)
@@ -622,7 +519,7 @@ class _BackboneFnPl(Function):
             if not need_dx:
                 break
             # block boundary: x is the ReLU output of the block below; its dz comes out of this epilogue
-            if wd is not None and blk.stride == 2 and COARSE_ADD and x.mask is not None:
+            if wd is not None and blk.stride == 2 and x.mask is not None:
                 # round 5: the downsample conv's data gradient stays on ITS grid (a plain 1x1 GEMM on a quarter of the
                 # pixels); conv1's data gradient adds it on the stride-2 lattice in its epilogue (round 4 scattered it
                 # into a full-resolution tensor, 3/4 zeros, and read that back: 0.92 ms per launch at layer3.0 / layer4.0)
@@ -634,8 +531,6 @@ class _BackboneFnPl(Function):
                 dz = dgrad(g1, _wt(w1), x.shape, 1, 1, 0, add=part, out=part, mask_y=x)
             else:
                 dz = dgrad(g1, _wt(w1), x.shape, 1, 1, 0, add=dz, mask_y=x)
-        if chains is not None:
-            ops._wait_stream(fork.main, fork.side)
         wg.join(*grads.values())
         out = []
         for w in ctx.plist:
@@ -703,8 +598,8 @@ class Backbone(nn.Module):
         self.prefix_stats["staged"] += 1
 
     def _fill(self) -> None:
-        """called once the current clip's forward has been queued — from the query decoder's entry (ops.run_deferred) or, with
-        STCAT_PREFIX_AT=backbone, right behind the backbone node: queue the staged clip's prefix on its lane"""
+        """called once the current clip's forward has been queued — from the query decoder's entry (ops.run_deferred): queue
+        the staged clip's prefix on its lane"""
         st, self._staged = self._staged, None
         if st is None or not ops.L.plane_count() or not _prefix_blocks(self.body):
             return
@@ -768,7 +663,7 @@ class Backbone(nn.Module):
         _prefix_range() frames, ~170 — launches otherwise cost the host thread 0.5 — 4 ms per step, which shows as soon as
         the host is busy: with a live process group the step is nearly host-bound).  The plan's only external tensor is
         the frame buffer; its output planes are the resident buffer of this slot, its temporaries live in its own pool."""
-        if not plans.ENABLED or ops.L.RECORDER is not None or frames.device.type != "cuda" or PREFIX_EAGER:
+        if not plans.ENABLED or ops.L.RECORDER is not None or frames.device.type != "cuda":
             _prefix_forward(frames, self.body, out)
             return
         pk = (key, self._pre_slot, tuple(frames.shape), frames.dtype, frames.data_ptr() % 16, self._prefix_state())
@@ -839,12 +734,11 @@ class Backbone(nn.Module):
             self.prefix_stats["taken" if pre is not None else "inline"] += 1
             feat = plans.apply(_BackboneFnPl, frames, self.body, pre.t if pre is not None else None,
                                pre.mask if pre is not None else None, *weights)
-            # the NEXT clip's frozen prefix, if one was declared (stage_next): behind this forward — at once, or handed to
-            # the query decoder's entry (ops.run_deferred in QueryDecoder.run), where the chip has room for it
-            if PREFIX_AT == "decoder" and self._staged is not None:
+            # the NEXT clip's frozen prefix, if one was declared (stage_next): handed to the query decoder's entry
+            # (ops.run_deferred in QueryDecoder.run), where the chip has room for it (queued right here, behind the backbone
+            # node: 78.36 against 78.11 ms per C3 step, profiles/r06_prefix_pipeline.log box Q)
+            if self._staged is not None:
                 ops.defer(self._fill)
-            else:
-                self._fill()
             return feat
         self._staged = None
         return plans.apply(_BackboneFn, frames, self.body, *weights)

@@ -7,11 +7,10 @@ layer's forward is a straight sequence of kernel launches and its backward is wr
 one autograd node per layer, gradient sums fused into the data-gradient epilogues (`add=`) or our own element-wise
 kernel, packed in-projection gradients written straight into their row blocks.  The kernels (and the reference call
 sites they replace) are the ones of `stcat_amd.ops`; only the host-side wiring differs, so every parity test of the
-model covers this path.  `STCAT_NO_COMPOSITE=1` switches back to the op-by-op wiring.
+model covers this path.  The docstrings of the nodes below cite the reference lines they implement.
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -19,9 +18,6 @@ from torch.autograd import Function
 
 from . import _lib as L
 from . import ops, plans
-
-ENABLED = not os.environ.get("STCAT_NO_COMPOSITE")
-
 
 class _Ctx:
     """the subset of the autograd ctx API that the Functions of stcat_amd.ops use"""
@@ -82,15 +78,7 @@ def _lin_b(g, x2, w, need_dx=True, dw=None, db=None, add=None, relu_y=None, want
                 add = add if add.is_contiguous() else add.contiguous()
             dx = (ops._zero_take(g, (M, K)) if (M <= 128 and N >= 128 and L.get_mma_mode() != "f32" and mask is None)
                   else None)
-            if mask is not None and mask[0] == "bits":
-                # the Linear's input was dropout(relu(.)) written by the plane kernel with its bit mask: data gradient on the
-                # A-stationary plane kernel (K_red = N = 256 -> 2048 columns), ReLU + dropout backward from the bits
-                _, ybits, gainvec, wtp = mask
-                gp = ops.pl_split(g)
-                dx = torch.empty(M, K, device=g.device, dtype=torch.float32)
-                L.call("stcat_pl_linear_dgrad_mask", gp.h, gp.l, wtp.h, wtp.l, ybits.data_ptr(), gainvec.data_ptr(),
-                       dx.data_ptr(), None, None, M, N, K, st)
-            elif mask is not None:
+            if mask is not None:
                 my, gain = mask
                 dx = torch.empty(M, K, device=g.device, dtype=torch.float32)
                 wt = ops.LINEAR_WT.get(w) if M > 256 else None
@@ -134,11 +122,7 @@ _BATCH = []          # stack of pending launch lists (innermost last)
 _DIRTY = [False]     # the side stream holds launches the current stream has not waited for yet
 
 
-DEFER_WGRADS = not os.environ.get("STCAT_NO_WGRAD_DEFER")
-
-
-INLINE_TIME_WGRADS = not os.environ.get("STCAT_TIME_WGRADS_DEFERRED")
-PROJ_LANE = not os.environ.get("STCAT_NO_PROJ_LANE")
+DEFER_WGRADS = True     # (graph.py turns it off around a hipGraph capture)
 
 
 def _wgrad(g, x2, dw, db, M, N, K):
@@ -212,8 +196,8 @@ class _Lane:
     makes the current stream wait for what the lane holds SO FAR (launches queued on the lane afterwards run beside the
     chain), `keep(...)` tells the allocator / the recording plan that the lane touches these tensors."""
 
-    def __init__(self, like: torch.Tensor, index: int, enabled: bool = True):
-        self.active = bool(enabled and ops.FORK_ENABLED and L._backend == "hip" and like.is_cuda)
+    def __init__(self, like: torch.Tensor, index: int):
+        self.active = bool(ops.FORK_ENABLED and L._backend == "hip" and like.is_cuda)
         if self.active:
             self.main = torch.cuda.current_stream(like.device)
             self.side = ops.side_stream(like.device, index)
@@ -273,14 +257,6 @@ def _outln_b(st, dy, need_da=True, mask=None):
     return d_a, d_res, dWo, dbo, dg, dbe
 
 
-FUSE_FFN = not os.environ.get("STCAT_NO_FFN_FUSE")
-
-
-FFN_PLANES = not os.environ.get("STCAT_NO_FFN_PLANES")
-FFN_PLANES_FULL = not os.environ.get("STCAT_NO_FFN_PLANES_FULL")
-QK_PLANES = not os.environ.get("STCAT_NO_QK_PLANES")    # (the spatial layers' q / k in-projection on the A-stationary kernel)    # (linear2 and both weight gradients on the plane kernels too)
-
-
 class FfnPlanes:
     """per-encoder cache for the FFN's wide side on the plane kernels (round 5): weight planes of linear1 (forward form)
     and linear2 (transposed form) of the layers whose token matrix is big enough, refreshed by ONE launch per forward pass,
@@ -322,7 +298,7 @@ def _ffn_f(x, W1, b1, W2, b2, g, be, p, pl=None):
     epilogue of linear2's data gradient (stcat_linear_dgrad_mask): per layer one [M, 2048] pass less forward (the dropout
     launch) and two less backward (dropout + ReLU backward) — 125 us per spatial encoder layer at C3 — and the pre-dropout
     activation is no longer kept.  The split-bf16 modes only; mma mode f32 keeps the separate launches."""
-    if FUSE_FFN and L.get_mma_mode() != "f32" and W1.shape[0] % 64 == 0 and W2.shape[0] % 64 == 0:
+    if L.get_mma_mode() != "f32" and W1.shape[0] % 64 == 0 and W2.shape[0] % 64 == 0:
         shp = x.shape
         K = shp[-1]
         x2 = x if x.dim() == 2 else x.reshape(-1, K)
@@ -338,25 +314,19 @@ def _ffn_f(x, W1, b1, W2, b2, g, be, p, pl=None):
             ymask = torch.empty(M, N // 8, device=x.device, dtype=torch.uint8)
             seed, off, base = ops._dropout_stream.take(M * N, x.device) if p > 0.0 else (0, 0, None)
             st_x = L.stream_of(x2)
-            if FFN_PLANES_FULL and W2.shape[0] % 64 == 0:
-                # ... its result stays in planes: linear2 (K = 2048 -> 256) runs on the plane tile kernel, and the backward
-                # pass reads the planes again (linear2's weight gradient); the fp32 [M, 2048] activation is never written
-                hp = ops.Planes.empty(x, M, N)
-                L.call("stcat_pl_linear_fwd", xp.h, xp.l, w1p.h, w1p.l, L._ptr(b1), None, None, hp.h, hp.l, ymask.data_ptr(),
-                       M, N, K, 1, float(p), seed, off, base, st_x)
-                D = W2.shape[0]
-                res2 = x.reshape(M, D)
-                res2 = res2 if res2.is_contiguous() else res2.contiguous()
-                h2 = torch.empty(M, D, device=x.device, dtype=torch.float32)
-                L.call("stcat_pl_linear_fwd", hp.h, hp.l, w2p.h, w2p.l, L._ptr(b2), res2.data_ptr() if p == 0.0 else None,
-                       h2.data_ptr(), None, None, None, M, D, N, 0, 0.0, 0, 0, None, st_x)
-                y, c_n = _f(ops.LayerNormFn, _T, h2.view(*shp[:-1], D), x if p > 0.0 else None, g, be, 1e-5, p)
-                return y, ("planes", c_n, xp, hp, ymask, gv, (w1t, w2t), (W1, W2), p, y.shape)
-            f1d = torch.empty(M, N, device=x.device, dtype=torch.float32)
-            L.call("stcat_pl_linear_fwd", xp.h, xp.l, w1p.h, w1p.l, L._ptr(b1), None, f1d.data_ptr(), None, None,
-                   ymask.data_ptr(), M, N, K, 1, float(p), seed, off, base, st_x)
-            y, st = _outln_f(f1d.view(*shp[:-1], N), W2, b2, x, g, be, p)
-            return y, (st, ("bits", ymask, gv, w2t), x2, f1d, W1)
+            # ... its result stays in planes: linear2 (K = 2048 -> 256) runs on the plane tile kernel, and the backward
+            # pass reads the planes again (linear2's weight gradient); the fp32 [M, 2048] activation is never written
+            hp = ops.Planes.empty(x, M, N)
+            L.call("stcat_pl_linear_fwd", xp.h, xp.l, w1p.h, w1p.l, L._ptr(b1), None, None, hp.h, hp.l, ymask.data_ptr(),
+                   M, N, K, 1, float(p), seed, off, base, st_x)
+            D = W2.shape[0]
+            res2 = x.reshape(M, D)
+            res2 = res2 if res2.is_contiguous() else res2.contiguous()
+            h2 = torch.empty(M, D, device=x.device, dtype=torch.float32)
+            L.call("stcat_pl_linear_fwd", hp.h, hp.l, w2p.h, w2p.l, L._ptr(b2), res2.data_ptr() if p == 0.0 else None,
+                   h2.data_ptr(), None, None, None, M, D, N, 0, 0.0, 0, 0, None, st_x)
+            y, c_n = _f(ops.LayerNormFn, _T, h2.view(*shp[:-1], D), x if p > 0.0 else None, g, be, 1e-5, p)
+            return y, ("planes", c_n, xp, hp, ymask, gv, (w1t, w2t), (W1, W2), p, y.shape)
         if p > 0.0:
             seed, off, base = ops._dropout_stream.take(M * N, x.device)
             f1d = torch.empty(M, N, device=x.device, dtype=torch.float32)
@@ -380,10 +350,6 @@ def _ffn_b(st, dy):
     if st[0] == "planes":
         return _ffn_b_planes(st, dy)
     st_o, c_dr, x_1, f1, W1 = st
-    if isinstance(c_dr, tuple) and c_dr[0] == "bits":
-        d_f1, d_x_res, dW2, db2, dg, dbe = _outln_b(st_o, dy, mask=c_dr)
-        d_x, dW1, db1, _ = _lin_b(d_f1, x_1, W1, add=d_x_res)
-        return d_x, dW1, db1, dW2, db2, dg, dbe
     if isinstance(c_dr, tuple) and c_dr[0] == "fused":
         d_f1, d_x_res, dW2, db2, dg, dbe = _outln_b(st_o, dy, mask=(f1, c_dr[1]))     # f1 = dropout(relu(.)) here
         d_x, dW1, db1, _ = _lin_b(d_f1, x_1, W1, add=d_x_res)
@@ -462,76 +428,58 @@ def _ln_b(st, dy, dg, dbe):
 # ------------------------------------------------------------------------------------------------------------------
 # encoder layer (modal_encoder.py:207-242), post-norm: 12 of them per step
 # ------------------------------------------------------------------------------------------------------------------
-class EncoderLayerFn(Function):
-    @staticmethod
-    def forward(ctx, x, pos, kpm, p, nhead, W_in, B_in, Wo, bo, g1, be1, W1, b1, W2, b2, g2, be2, ffn_pl=None):
-        D = x.shape[-1]
-        shp = x.shape
-        x = x if x.is_contiguous() else x.contiguous()
-        pos_b = pos if pos.shape == x.shape else pos.expand_as(x)
-        wqk = ffn_pl[0].get(("qk", W_in.data_ptr())) if (ffn_pl is not None and QK_PLANES) else None
-        if wqk is not None:
-            # q = k = src + pos as planes in ONE pass, the [M, 2D] in-projection on the A-stationary plane kernel (round 5)
-            qk_in, qkp = ops.pl_split_sum(x, pos_b if pos_b.is_contiguous() else pos_b.contiguous())
-            M_ = qk_in.numel() // D
-            qk = torch.empty(*shp[:-1], 2 * D, device=x.device, dtype=torch.float32)
-            L.call("stcat_pl_linear_fwd", qkp.h, qkp.l, wqk.h, wqk.l, B_in[:2 * D].data_ptr(), None, qk.data_ptr(), None, None,
-                   None, M_, 2 * D, D, 0, 0.0, 0, 0, None, L.stream_of(x))
-            x_qk = qk_in.view(M_, D)
-        else:
-            qk_in = ops.ew(L.EW_ADD, x, pos_b if pos_b.is_contiguous() else pos_b.contiguous())      # q = k = src + pos :234
-            qk, x_qk = _lin_f(qk_in, W_in[:2 * D], B_in[:2 * D])
-        v, x_v = _lin_f(x, W_in[2 * D:], B_in[2 * D:])
-        (a, _), c_att = _f(ops.MhaSelfFn, (True, False, True) + (False,) * 5, qk, qk[:, :, D:], v, kpm,
-                           (D // nhead) ** -0.5, False, True, p)
-        x1, st1 = _outln_f(a, Wo, bo, x, g1, be1, p)
-        y, st2 = _ffn_f(x1, W1, b1, W2, b2, g2, be2, p, pl=ffn_pl)
-        ctx.st = (c_att, st1, st2, x_qk, x_v, D, shp, pos.shape)
-        ctx.W_in = W_in
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        with wgrad_batch(dy):
-            return EncoderLayerFn._backward(ctx, dy)
-
-    @staticmethod
-    def _backward(ctx, dy):
-        (c_att, st1, st2, x_qk, x_v, D, shp, pos_shape) = ctx.st
-        W_in = ctx.W_in
-        need_x, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        d_x1, dW1, db1, dW2, db2, dg2, dbe2 = _ffn_b(st2, dy)
-        d_a, d_x_res, dWo, dbo, dg1, dbe1 = _outln_b(st1, d_x1)
-        r = ops.MhaSelfFn.backward(c_att, d_a.view(shp), None)
-        dqk, dv = r[0], r[2]
-        dW_in = ops._zeros(dy, 3 * D, D)        # packed in-projection gradient: the two GEMMs write its row blocks
-        dB_in = ops._zeros(dy, 3 * D)
-        d_x, _, _, _ = _lin_b(dv, x_v, W_in[2 * D:], need_dx=need_x, dw=dW_in[2 * D:], db=dB_in[2 * D:],
-                              add=d_x_res if need_x else None)
-        d_pos = None
-        if need_pos:
-            d_qkin, _, _, _ = _lin_b(dqk, x_qk, W_in[:2 * D], dw=dW_in[:2 * D], db=dB_in[:2 * D])
-            if need_x:
-                d_x = _add(d_x, d_qkin)
-            d_pos = d_qkin.view(shp)
-            if tuple(pos_shape) != tuple(shp):
-                d_pos = d_pos.sum_to_size(pos_shape)
-        else:
-            d_x, _, _, _ = _lin_b(dqk, x_qk, W_in[:2 * D], need_dx=need_x, dw=dW_in[:2 * D], db=dB_in[:2 * D],
-                                  add=d_x if need_x else None)
-        return ((d_x.view(shp) if d_x is not None else None), d_pos, None, None, None, dW_in, dB_in, dWo, dbo, dg1, dbe1,
-                dW1, db1, dW2, db2, dg2, dbe2)
+def _enc_layer_f(x, pos, kpm, p, nhead, W_in, B_in, Wo, bo, g1, be1, W1, b1, W2, b2, g2, be2, ffn_pl=None):
+    """x, pos: [B,S,256] batch-first (pos may be [1,S,256]); kpm [B,S] bytes or None -> (y, state).  q = k = src + pos
+    (modal_encoder.py:234), value = src (:236), out-projection + norm1 (:237-238), FFN + norm2 (:239-241)."""
+    D = x.shape[-1]
+    shp = x.shape
+    x = x if x.is_contiguous() else x.contiguous()
+    pos_b = pos if pos.shape == x.shape else pos.expand_as(x)
+    wqk = ffn_pl[0].get(("qk", W_in.data_ptr())) if ffn_pl is not None else None
+    if wqk is not None:
+        # q = k = src + pos as planes in ONE pass, the [M, 2D] in-projection on the A-stationary plane kernel (round 5)
+        qk_in, qkp = ops.pl_split_sum(x, pos_b if pos_b.is_contiguous() else pos_b.contiguous())
+        M_ = qk_in.numel() // D
+        qk = torch.empty(*shp[:-1], 2 * D, device=x.device, dtype=torch.float32)
+        L.call("stcat_pl_linear_fwd", qkp.h, qkp.l, wqk.h, wqk.l, B_in[:2 * D].data_ptr(), None, qk.data_ptr(), None, None,
+               None, M_, 2 * D, D, 0, 0.0, 0, 0, None, L.stream_of(x))
+        x_qk = qk_in.view(M_, D)
+    else:
+        qk_in = ops.ew(L.EW_ADD, x, pos_b if pos_b.is_contiguous() else pos_b.contiguous())      # q = k = src + pos :234
+        qk, x_qk = _lin_f(qk_in, W_in[:2 * D], B_in[:2 * D])
+    v, x_v = _lin_f(x, W_in[2 * D:], B_in[2 * D:])
+    (a, _), c_att = _f(ops.MhaSelfFn, (True, False, True) + (False,) * 5, qk, qk[:, :, D:], v, kpm,
+                       (D // nhead) ** -0.5, False, True, p)
+    x1, st1 = _outln_f(a, Wo, bo, x, g1, be1, p)
+    y, st2 = _ffn_f(x1, W1, b1, W2, b2, g2, be2, p, pl=ffn_pl)
+    return y, (c_att, st1, st2, x_qk, x_v, D, shp, pos.shape, W_in)
 
 
-def encoder_layer(layer, x, pos, kpm, pos_is_const: bool):
-    a = layer.self_attn
-    p = layer.dropout_p if layer.training else 0.0
-    if pos_is_const:
-        pos = pos.detach()
-    return EncoderLayerFn.apply(x, pos, kpm, p, layer.nhead, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight,
-                                a.out_proj.bias, layer.norm1.weight, layer.norm1.bias, layer.linear1.weight,
-                                layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm2.weight,
-                                layer.norm2.bias)
+def _enc_layer_b(st, dy, need_x, need_pos):
+    """-> (d_x, d_pos | None, dW_in, dB_in, dWo, dbo, dg1, dbe1, dW1, db1, dW2, db2, dg2, dbe2); the weight gradients go
+    through _wgrad: the caller opens the wgrad_batch"""
+    (c_att, st1, st2, x_qk, x_v, D, shp, pos_shape, W_in) = st
+    d_x1, dW1, db1, dW2, db2, dg2, dbe2 = _ffn_b(st2, dy)
+    d_a, d_x_res, dWo, dbo, dg1, dbe1 = _outln_b(st1, d_x1)
+    r = ops.MhaSelfFn.backward(c_att, d_a.view(shp), None)
+    dqk, dv = r[0], r[2]
+    dW_in = ops._zeros(dy, 3 * D, D)        # packed in-projection gradient: the two GEMMs write its row blocks
+    dB_in = ops._zeros(dy, 3 * D)
+    d_x, _, _, _ = _lin_b(dv, x_v, W_in[2 * D:], need_dx=need_x, dw=dW_in[2 * D:], db=dB_in[2 * D:],
+                          add=d_x_res if need_x else None)
+    d_pos = None
+    if need_pos:
+        d_qkin, _, _, _ = _lin_b(dqk, x_qk, W_in[:2 * D], dw=dW_in[:2 * D], db=dB_in[:2 * D])
+        if need_x:
+            d_x = _add(d_x, d_qkin)
+        d_pos = d_qkin.view(shp)
+        if tuple(pos_shape) != tuple(shp):
+            d_pos = d_pos.sum_to_size(pos_shape)
+    else:
+        d_x, _, _, _ = _lin_b(dqk, x_qk, W_in[:2 * D], need_dx=need_x, dw=dW_in[:2 * D], db=dB_in[:2 * D],
+                              add=d_x if need_x else None)
+    return ((d_x.view(shp) if d_x is not None else None), d_pos, dW_in, dB_in, dWo, dbo, dg1, dbe1,
+            dW1, db1, dW2, db2, dg2, dbe2)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -543,7 +491,10 @@ _NT_LAYER = 18
 class TimeDecoderFn(Function):
     """inputs: memory [n,S',D], pos [n,S',D] (constant), kpm, query_pos [T,D], time_pos [T,D] (constant) ->
     (hs [L,T,D], head-mean self-attention weights [L,1,T,T]).  Each layer projects (memory + pos) / memory with the
-    key / value rows of its packed cross_attn_image in-projection (:633-639); the packed gradients are written in place."""
+    key / value rows of its packed cross_attn_image in-projection (:633-639); the packed gradients are written in place.
+    Per layer (query_decoder.py): q = k = tgt + (query_pos + time) :602, self-attention with head-mean weights :604-610,
+    out-projection + norm1 :611-613, cross-attention query = tgt + query_pos :633-634 on keys of memory + pos :636,
+    out-projection + norm3 :653-654, FFN + norm4 :657-659; the decoder's shared norm on every layer's state :526-536."""
 
     @staticmethod
     def forward(ctx, memory, pos, kpm, query_pos, time_pos, p, nhead, nl, gN, beN, *prm):
@@ -593,14 +544,11 @@ class TimeDecoderFn(Function):
         # first (the host replays the box decoder's backward before this one): this node's ~100 launches queued behind them
         # and its final join — which the encoder's backward waits for — came 0.9 ms after the box decoder had finished
         # (tools/node_times.py: 3.75 ms against 2.86 ms).  Inline they lengthen this chain to ~2.8 ms, still the shorter one.
-        if INLINE_TIME_WGRADS:
-            _BATCH.append(None)          # (a None frame: _wgrad launches directly, nested flushes are no-ops)
-            try:
-                return TimeDecoderFn._backward(ctx, d_hs, d_ws)
-            finally:
-                _BATCH.pop()
-        with wgrad_batch(d_hs):
+        _BATCH.append(None)          # (a None frame: _wgrad launches directly, nested flushes are no-ops)
+        try:
             return TimeDecoderFn._backward(ctx, d_hs, d_ws)
+        finally:
+            _BATCH.pop()
 
     @staticmethod
     def _backward(ctx, d_hs, d_ws):
@@ -679,7 +627,12 @@ class BoxDecoderFn(Function):
     (hs [L,T,D], refs [L,T,4]).  Each layer projects the memory itself (ca_kcontent_proj / ca_kpos_proj / ca_v_proj,
     query_decoder.py:355-358), so the key / value gradients feed that layer's weight and data gradients directly.
     Shared modules (ref_point_head, query_scale, bbox_embed, norm) accumulate their gradients over the layers inside
-    the node instead of through L AccumulateGrad adds."""
+    the node instead of through L AccumulateGrad adds.
+    Per layer (query_decoder.py): sine embedding of the anchor :190, ref_point_head :191, query_scale :194-200; the layer
+    itself — q / k = content + time + position projections :329-338, nn.MultiheadAttention in-projection :341,
+    out-projection + norm1 :343-345, memory-side projections :355-358 (+ position terms in the first layer :360-366),
+    sine projection :369, one-query cross-attention :368-409, out-projection + norm3 :431-432, FFN + norm4 :435-437;
+    anchor update :212-219, shared norm :221-229.  The box head of pipeline.py:88-93 runs here too (third output)."""
 
     @staticmethod
     def forward(ctx, memory, pos, kpm, anchor, time_embed, p, nhead, nl, *prm):
@@ -701,7 +654,7 @@ class BoxDecoderFn(Function):
         # query_decoder.py:355-358 — three [n*S', 256] x 256 GEMMs, 72 us of a layer's 370 us chain at C3) do not depend on
         # the query state: layer i + 1's run on a second lane (the weight-gradient stream, idle in the forward pass) while
         # the chain works through layer i; the chain waits for them right before its cross-attention.
-        lane = _Lane(memory, 1, PROJ_LANE)
+        lane = _Lane(memory, 1)
         x_pos, x_mem = pos.reshape(-1, D), memory.reshape(-1, D)
         rows = x_mem.shape[0]
 
@@ -1024,23 +977,21 @@ class EncoderFn(Function):
         video = video_cls.view(1, d)
         ctxs = []
         ffn_pl = None
-        if (wpc is not None and FFN_PLANES and FUSE_FFN and L.get_mma_mode() == "bf16x6p" and n * S1 >= 4096 and d == 256
+        if (wpc is not None and L.get_mma_mode() == "bf16x6p" and n * S1 >= 4096 and d == 256
                 and vis_tokens.is_cuda):
             # the spatial layers' FFN (13 248 x 256 -> 2048 at C3) on the plane kernels: ONE refresh of their weight planes
             pairs = [(prm[(2 * i) * _NE_LAYER + 6], prm[(2 * i) * _NE_LAYER + 8]) for i in range(nl)]
             need_bwd = any(w.requires_grad for pr in pairs for w in pr)
-            wqks = [prm[(2 * i) * _NE_LAYER][:2 * d] for i in range(nl)] if QK_PLANES else []     # q / k rows of W_in
+            wqks = [prm[(2 * i) * _NE_LAYER][:2 * d] for i in range(nl)]     # q / k rows of W_in: their in-projection too
             ffn_pl = (wpc.refresh(pairs, need_bwd, extra=wqks), wpc)
         for i in range(nl):
             sp = prm[(2 * i) * _NE_LAYER:(2 * i + 1) * _NE_LAYER]
             tp = prm[(2 * i + 1) * _NE_LAYER:(2 * i + 2) * _NE_LAYER]
-            c_s = _Ctx((True, True))
-            x1 = EncoderLayerFn.forward(c_s, x, pos, kpm, p, nhead, *sp, ffn_pl=ffn_pl)        # :163-168
+            x1, c_s = _enc_layer_f(x, pos, kpm, p, nhead, *sp, ffn_pl=ffn_pl)                  # :163-168
             seq = ops._empty(x, 1, n + 1, d)                                                   # :170-177
             ops.ew(L.EW_COPY, video, out=seq[0, 0:1])
             ops.ew2d(L.EW_COPY, _cols(x1, 0, 1), out=seq[0, 1:])
-            c_t = _Ctx((True, False))
-            seq2 = EncoderLayerFn.forward(c_t, seq, tpos, None, p, nhead, *tp)                 # :180-185
+            seq2, c_t = _enc_layer_f(seq, tpos, None, p, nhead, *tp)                           # :180-185
             video = seq2[0, 0:1]                                                               # :190
             ops.ew2d(L.EW_COPY, seq2[0, 1:], out=_cols(x1, 0, 1))                              # :195 (in place there too)
             x = x1
@@ -1075,13 +1026,15 @@ class EncoderFn(Function):
             d_seq2 = ops._empty(like, 1, n + 1, d)
             ops.ew(L.EW_COPY, d_video, out=d_seq2[0, 0:1])
             ops.ew2d(L.EW_COPY, _cols(d_x, 0, 1), out=d_seq2[0, 1:])
-            r = EncoderLayerFn.backward(c_t, d_seq2)          # (its own wgrad_batch: flushed per layer, joined at the end)
-            grads[2 * i + 1] = r[5:]
+            with wgrad_batch(d_seq2):                         # (its own wgrad_batch: flushed per layer, joined at the end)
+                r = _enc_layer_b(c_t, d_seq2, True, False)    # (tpos is constant)
+            grads[2 * i + 1] = r[2:]
             d_seq = r[0]
             d_video = d_seq[0, 0:1]
             ops.ew2d(L.EW_COPY, d_seq[0, 1:], out=_cols(d_x, 0, 1))       # the [CLS] slots of x1 fed the temporal layer
-            r = EncoderLayerFn.backward(c_s, d_x)
-            grads[2 * i] = r[5:]
+            with wgrad_batch(d_x):
+                r = _enc_layer_b(c_s, d_x, True, True)
+            grads[2 * i] = r[2:]
             d_x, d_pos = r[0], r[1]
             if d_lp is None:
                 d_lp = ops.ew2d(L.EW_COPY, _cols(d_pos, 0, 1))

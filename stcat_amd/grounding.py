@@ -64,25 +64,6 @@ def _lin(m: nn.Linear, x, res=None, relu=False):
     return ops.linear(x, m.weight, m.bias, res=res, relu=relu)
 
 
-def _ln(m: nn.LayerNorm, x):
-    return ops.layer_norm(x, m.weight, m.bias, eps=m.eps)
-
-
-def _ln_res(m: nn.LayerNorm, w, b, x, res, p: float):
-    """LayerNorm(res + dropout_p(x W^T + b)).  Eval (p = 0): the residual rides in the GEMM epilogue.  Train: the
-    dropout and the residual add happen inside the LayerNorm kernel (no separate dropout pass)."""
-    if p > 0.0:
-        return ops.layer_norm(ops.linear(x, w, b), m.weight, m.bias, res=res, eps=m.eps, drop_p=p)
-    return ops.layer_norm(ops.linear(x, w, b, res=res), m.weight, m.bias, eps=m.eps)
-
-
-def _ffn_ln(norm: nn.LayerNorm, layer, x, p: float):
-    """norm(x + dropout(linear2(dropout(relu(linear1 x)))))  (modal_encoder.py:239-241; query_decoder.py:435-437,
-    657-659)"""
-    h = ops.dropout(_lin(layer.linear1, x, relu=True), p)
-    return _ln_res(norm, layer.linear2.weight, layer.linear2.bias, h, x, p)
-
-
 def _xavier(module: nn.Module):
     for p in module.parameters():
         if p.dim() > 1:
@@ -106,21 +87,6 @@ class TransformerEncoderLayer(nn.Module):
         self.nhead = nhead
         self.dropout_p = dropout
 
-    def run(self, x, pos, kpm, pos_is_const: bool):
-        """x, pos: [B,S,256] batch-first; kpm [B,S] bool or None."""
-        if composite.ENABLED:  # one autograd node per layer, hand-written backward (stcat_amd/composite.py)
-            return composite.encoder_layer(self, x, pos, kpm, pos_is_const)
-        D = x.shape[-1]
-        p = self.dropout_p if self.training else 0.0
-        (Wqk, Wv), (Bqk, Bv) = (ops.split_rows(self.self_attn.in_proj_weight, (2 * D, D)),
-                                ops.split_rows(self.self_attn.in_proj_bias, (2 * D, D)))
-        qk_in = ops.add_const(x, pos) if pos_is_const else ops.add(x, pos)      # q = k = src + pos   :234
-        qk = ops.linear(qk_in, Wqk, Bqk)                                        # packed q|k projection
-        v = ops.linear(x, Wv, Bv)                                               # value = src         :236
-        a, _ = ops.mha_self_packed(qk, v, kpm, (D // self.nhead) ** -0.5, drop_p=p)
-        x = _ln_res(self.norm1, self.self_attn.out_proj.weight, self.self_attn.out_proj.bias, a, x, p)   # :237-238
-        return _ffn_ln(self.norm2, self, x, p)                                  # :239-241
-
 
 class SpatialTemporalEncoder(nn.Module):
     """modal_encoder.py:104-204."""
@@ -137,23 +103,6 @@ class SpatialTemporalEncoder(nn.Module):
         self.video_cls = nn.Embedding(1, d_model)
         self.num_layers = num_layers
         self.d_model = d_model
-
-    def run(self, tokens, kpm, pos):
-        """tokens/pos [n, S', 256] (visual + text rows), kpm [n, S'] -> (memory [n,S',256], frames_cls [n,256],
-        video_cls [1,256]) for one video of n frames."""
-        n, _, d = tokens.shape
-        x = torch.cat([self.frame_cls.weight[None].expand(n, 1, d), tokens], dim=1)          # :145-149
-        pos = torch.cat([self.local_pos_embed.weight[None].expand(n, 1, d), pos], dim=1)     # :151
-        kpm = torch.cat([torch.zeros(n, 1, dtype=torch.bool, device=kpm.device), kpm], dim=1)
-        video = self.video_cls.weight                                                        # [1,256]  :154
-        tpos = self.time_embed(n + 1)[:, 0, :][None]                                         # [1,n+1,256] :155
-        for i in range(self.num_layers):
-            x = self.spatial_layers[i].run(x, pos, kpm, pos_is_const=False)                  # :163-168
-            seq = torch.cat([video, x[:, 0, :]], dim=0)[None]                                # [1,n+1,256] :170-177
-            seq = self.temporal_layers[i].run(seq, tpos, None, pos_is_const=True)            # :180-185
-            video = seq[0, 0:1]                                                              # :190
-            x = torch.cat([seq[0, 1:, None, :], x[:, 1:, :]], dim=1)                         # :195 (in place there)
-        return x[:, 1:, :], x[:, 0, :], video
 
 
 class CrossModalEncoder(plans.InvalidatesPlans, nn.Module):
@@ -179,27 +128,17 @@ class CrossModalEncoder(plans.InvalidatesPlans, nn.Module):
         """vis_tokens/vis_pos [n,HW,256], vis_mask [n,HW] bool, text_mask [1,L] bool, text_mem [L,1,256]."""
         n, hw, d = vis_tokens.shape
         L = text_mem.shape[0]
-        if composite.ENABLED:
-            # masks (bytes, 1 = padding): column 0 = the frame [CLS] slot the encoder prepends (:147), then the visual
-            # tokens with token 0 forced valid (:46), then the text; built once, shared by all 24 attention layers
-            full = torch.zeros(n, 1 + hw + L, dtype=torch.uint8, device=vis_tokens.device)
-            full[:, 1:1 + hw] = vis_mask
-            full[:, 1] = 0
-            full[:, 1 + hw:] = text_mask[0:1]
-            mask = full[:, 1:].contiguous()
-            pos = ops._zeros(vis_tokens, n, hw + L, d)                                       # :82
-            ops.ew2d(ops.L.EW_COPY, vis_pos.contiguous().view(n, hw * d), out=pos.view(n, (hw + L) * d)[:, :hw * d])
-            tpos = self.encoder.time_embed(n + 1)[:, 0, :][None]                             # [1,n+1,256] :155
-            memory, frames_cls, video_cls = composite.encoder(self.encoder, vis_tokens, text_mem[:, 0, :], vis_pos,
-                                                              full, tpos)
-            return memory, mask, frames_cls, video_cls, pos
-        vis_mask = vis_mask.clone()
-        vis_mask[:, 0] = False                                                               # :46
-        txt = text_mem[:, 0, :][None].expand(n, L, d)                                        # :70-77
-        tokens = torch.cat([vis_tokens, txt], dim=1)                                         # :80
-        mask = torch.cat([vis_mask, text_mask[0:1].expand(n, L)], dim=1)                     # :81
-        pos = torch.cat([vis_pos, torch.zeros(n, L, d, device=vis_pos.device)], dim=1)       # :82
-        memory, frames_cls, video_cls = self.encoder.run(tokens, mask, pos)
+        # masks (bytes, 1 = padding): column 0 = the frame [CLS] slot the encoder prepends (:147), then the visual
+        # tokens with token 0 forced valid (:46), then the text (:81); built once, shared by all 24 attention layers
+        full = torch.zeros(n, 1 + hw + L, dtype=torch.uint8, device=vis_tokens.device)
+        full[:, 1:1 + hw] = vis_mask
+        full[:, 1] = 0
+        full[:, 1 + hw:] = text_mask[0:1]
+        mask = full[:, 1:].contiguous()
+        pos = ops._zeros(vis_tokens, n, hw + L, d)                                           # :82
+        ops.ew2d(ops.L.EW_COPY, vis_pos.contiguous().view(n, hw * d), out=pos.view(n, (hw + L) * d)[:, :hw * d])
+        tpos = self.encoder.time_embed(n + 1)[:, 0, :][None]                                 # [1,n+1,256] :155
+        memory, frames_cls, video_cls = composite.encoder(self.encoder, vis_tokens, text_mem[:, 0, :], vis_pos, full, tpos)
         return memory, mask, frames_cls, video_cls, pos
 
     def forward(self, videos: NestedTensor = None, vis_pos=None, texts: Tuple = None) -> Dict:
@@ -268,35 +207,6 @@ class TransformerDecoderLayer(nn.Module):
         self.nhead = nhead
         self.dropout_p = dropout
 
-    def run(self, tgt, kc, kpos, vv, kpm, query_pos, time_embed, query_sine, first: bool):
-        """tgt/query_pos/time_embed/query_sine [T,256]; kc/kpos/vv [n,S',256] = this layer's ca_kcontent_proj(memory),
-        ca_kpos_proj(pos), ca_v_proj(memory) — column blocks of the layer-batched projections (QueryDecoder.run)."""
-        T, D = tgt.shape
-        hd = D // self.nhead
-        p = self.dropout_p if self.training else 0.0
-        W, Bi = self.self_attn.in_proj_weight, self.self_attn.in_proj_bias
-        q = ops.add3(_lin(self.sa_qcontent_proj, tgt), _lin(self.sa_qtime_proj, time_embed),
-                     _lin(self.sa_qpos_proj, query_pos))                                     # :329-338
-        k = ops.add3(_lin(self.sa_kcontent_proj, tgt), _lin(self.sa_ktime_proj, time_embed),
-                     _lin(self.sa_kpos_proj, query_pos))
-        v = _lin(self.sa_v_proj, tgt)
-        (Wq, Wk, Wv), (Bq, Bk, Bv) = ops.split_rows(W, (D, D, D)), ops.split_rows(Bi, (D, D, D))
-        qp = ops.linear(q, Wq, Bq)                                                           # nn.MHA in-proj :341
-        kp_ = ops.linear(k, Wk, Bk)
-        vp = ops.linear(v, Wv, Bv)
-        a, _ = ops.mha_self(qp[None], kp_[None], vp[None], None, hd ** -0.5, drop_p=p)
-        tgt = _ln_res(self.norm1, self.self_attn.out_proj.weight, self.self_attn.out_proj.bias, a[0], tgt, p)
-
-        qc = _lin(self.ca_qcontent_proj, tgt)
-        if first:                                                                            # :360-366
-            qc = ops.add(qc, _lin(self.ca_qpos_proj, query_pos))
-            kpos = kpos.contiguous()  # k1 and k2 must share one leading dimension in the kernel
-            kc = ops.add(kc.contiguous(), kpos)
-        qs = _lin(self.ca_qpos_sine_proj, query_sine)                                        # :369
-        a = ops.attn_q1(qc, qs, kc, kpos, vv, kpm, (2 * hd) ** -0.5, drop_p=p)               # :368-409
-        tgt = _ln_res(self.norm3, self.cross_attn.out_proj.weight, self.cross_attn.out_proj.bias, a, tgt, p)  # :431
-        return _ffn_ln(self.norm4, self, tgt, p)                                             # :435-437
-
 
 class TransformerDecoder(nn.Module):
     """query_decoder.py:150-247."""
@@ -313,38 +223,10 @@ class TransformerDecoder(nn.Module):
         for layer_id in range(num_layers - 1):
             self.layers[layer_id + 1].ca_qpos_proj = None                                    # :166-167
 
-    def memory_projections(self, memory, pos):
-        """ca_kcontent_proj / ca_v_proj of `memory` and ca_kpos_proj of `pos` for ALL layers as three GEMMs
-        with N = layers*256 (query_decoder.py:355-358 computes them layer by layer on the same inputs)."""
-        L_ = self.num_layers
-        cat = lambda nm, leaf: torch.cat([getattr(getattr(l, nm), leaf) for l in self.layers], dim=0)  # noqa: E731
-        kc = ops.split_cols(ops.linear(memory, cat("ca_kcontent_proj", "weight"), cat("ca_kcontent_proj", "bias")), L_)
-        vv = ops.split_cols(ops.linear(memory, cat("ca_v_proj", "weight"), cat("ca_v_proj", "bias")), L_)
-        kp = ops.split_cols(ops.linear(pos, cat("ca_kpos_proj", "weight"), cat("ca_kpos_proj", "bias")), L_)
-        return kc, kp, vv
-
     def run(self, memory, kpm, pos, anchor, time_embed):
-        """memory/pos [n,S',256]; anchor [T,4] (sigmoid-ed template); returns hs [L,T,256], refs [L,T,4]."""
-        T = anchor.shape[0]
-        if composite.ENABLED:
-            return composite.box_decoder(self, memory, pos, kpm, anchor, time_embed)
-        kc, kp, vv = self.memory_projections(memory, pos)
-        out = torch.zeros(T, self.d_model, device=memory.device)
-        inter, refs = [], [anchor]
-        for i, layer in enumerate(self.layers):
-            sine = ops.sine_embed(anchor)                                                    # [T,512]  :190
-            query_pos = self.ref_point_head(sine)                                            # :191
-            sine_q = sine[:, : self.d_model]
-            if i > 0:
-                sine_q = ops.mul(sine_q.contiguous(), self.query_scale(out))                 # :194-200
-            out = layer.run(out, kc[i], kp[i], vv[i], kpm, query_pos, time_embed, sine_q, i == 0)
-            tmp = self.bbox_embed(out)                                                       # :212
-            new_anchor = ops.sigmoid(ops.add(tmp, ops.inverse_sigmoid(anchor)))              # :213-214
-            if i != self.num_layers - 1:
-                refs.append(new_anchor)
-            anchor = new_anchor.detach()                                                     # :219
-            inter.append(_ln(self.norm, out))                                                # :221-229
-        return torch.stack(inter), torch.stack(refs)
+        """memory/pos [n,S',256]; anchor [T,4] (sigmoid-ed template); returns hs [L,T,256], refs [L,T,4] and the box
+        head's coord [L,T,4] (pipeline.py:88-93), evaluated inside the decoder node."""
+        return composite.box_decoder(self, memory, pos, kpm, anchor, time_embed)
 
 
 class TimeDecoderLayer(nn.Module):
@@ -362,25 +244,6 @@ class TimeDecoderLayer(nn.Module):
         self.nhead = nhead
         self.dropout_p = dropout
 
-    def run(self, tgt, kc, vv, kpm, query_pos, qpos_time, Wcq, Bcq):
-        """kc/vv [n,S',256]: this layer's key / value in-projection of (memory + pos) / memory; Wcq/Bcq: the query
-        rows of cross_attn_image's packed in-projection (split once in TimeDecoder.run)."""
-        T, D = tgt.shape
-        hd = D // self.nhead
-        p = self.dropout_p if self.training else 0.0
-        (Wqk, Wv), (Bqk, Bv) = (ops.split_rows(self.self_attn.in_proj_weight, (2 * D, D)),
-                                ops.split_rows(self.self_attn.in_proj_bias, (2 * D, D)))
-        qk_in = ops.add(tgt, qpos_time)                                                      # :602
-        qk = ops.linear(qk_in, Wqk, Bqk)
-        v = ops.linear(tgt, Wv, Bv)
-        a, w = ops.mha_self_packed(qk[None], v[None], None, hd ** -0.5, need_weights=True, drop_p=p)   # :604-610
-        tgt = _ln_res(self.norm1, self.self_attn.out_proj.weight, self.self_attn.out_proj.bias, a[0], tgt, p)
-        qc = ops.linear(ops.add(tgt, query_pos), Wcq, Bcq)                                   # :633-634
-        a = ops.attn_q1(qc, None, kc, None, vv, kpm, hd ** -0.5, drop_p=p)
-        tgt = _ln_res(self.norm3, self.cross_attn_image.out_proj.weight, self.cross_attn_image.out_proj.bias,
-                      a, tgt, p)                                                             # :653-654
-        return _ffn_ln(self.norm4, self, tgt, p), w                                          # :657-659
-
 
 class TimeDecoder(nn.Module):
     """query_decoder.py:478-550."""
@@ -390,29 +253,6 @@ class TimeDecoder(nn.Module):
         self.layers = nn.ModuleList(TimeDecoderLayer(d_model, nhead, ffn, dropout) for _ in range(num_layers))
         self.norm = nn.LayerNorm(d_model)
         self.d_model = d_model
-
-    def run(self, memory, mem_pos, kpm, query_pos, time_pos):
-        """memory, mem_pos (= memory + pos) [n,S',256].  The key/value in-projections of all layers run as two
-        GEMMs with N = layers*256 (query_decoder.py:633-639 applies them per layer to the same tensors)."""
-        T = query_pos.shape[0]
-        D = self.d_model
-        nl = len(self.layers)
-        wparts = [ops.split_rows(l.cross_attn_image.in_proj_weight, (D, D, D)) for l in self.layers]
-        bparts = [ops.split_rows(l.cross_attn_image.in_proj_bias, (D, D, D)) for l in self.layers]
-        Wk = torch.cat([w[1] for w in wparts], dim=0)
-        Bk = torch.cat([b[1] for b in bparts], dim=0)
-        Wv = torch.cat([w[2] for w in wparts], dim=0)
-        Bv = torch.cat([b[2] for b in bparts], dim=0)
-        kc = ops.split_cols(ops.linear(mem_pos, Wk, Bk), nl)
-        vv = ops.split_cols(ops.linear(memory, Wv, Bv), nl)
-        out = torch.zeros(T, self.d_model, device=memory.device)
-        qpos_time = ops.add_const(query_pos, time_pos)                                       # query_pos + time :602
-        inter, ws = [], []
-        for i, layer in enumerate(self.layers):
-            out, w = layer.run(out, kc[i], vv[i], kpm, query_pos, qpos_time, wparts[i][0], bparts[i][0])
-            inter.append(_ln(self.norm, out))
-            ws.append(w)
-        return torch.stack(inter), torch.stack(ws)
 
 
 class QueryDecoder(plans.InvalidatesPlans, nn.Module):
@@ -443,8 +283,10 @@ class QueryDecoder(plans.InvalidatesPlans, nn.Module):
         n, S, d = memory.shape
         T = frames_cls.shape[0]
         assert n == T
-        if PREFIX_TRIGGER == "entry":
-            ops.run_deferred()   # (round 6: the next clip's frozen backbone prefix starts here, under the decoders' chains)
+        # round 6: the next clip's frozen backbone prefix starts here, under the decoders' chains (measured and rejected: queued
+        # at this method's exit, under the decoders' backward only — 77.66 ms per C3 step against 77.16 here,
+        # profiles/r06_prefix_pipeline.log)
+        ops.run_deferred()
         pos_query, temp_query = self.template_generator.run(frames_cls, video_cls)          # :97-99
         anchor = ops.sigmoid(pos_query)                                                      # :101
         time_embed = self.time_embed(T)[:, 0, :]                                             # :120
@@ -456,19 +298,9 @@ class QueryDecoder(plans.InvalidatesPlans, nn.Module):
         #  created outside the measured set they serialise with one of the step's queues: profiles/r06_prefix_pipeline.log)
         fork = ops.fork_stream(memory)
         with fork:
-            if composite.ENABLED:
-                time_hs, weights = composite.time_decoder(self.temp_decoder, memory, mem_pos, mem_kpm, temp_query,
-                                                          time_embed)
-            else:
-                mem_plus_pos = ops.add_const(memory, mem_pos)                                # memory + pos  :636
-                time_hs, weights = self.temp_decoder.run(memory, mem_plus_pos, mem_kpm, temp_query.contiguous(),
-                                                         time_embed)
-        dec_out = self.decoder.run(memory, mem_kpm, mem_pos, anchor, time_embed)
-        hs, ref = dec_out[0], dec_out[1]
-        self.last_coord = dec_out[2] if len(dec_out) > 2 else None    # the box head, evaluated inside the decoder node
+            time_hs, weights = composite.time_decoder(self.temp_decoder, memory, mem_pos, mem_kpm, temp_query, time_embed)
+        hs, ref, self.last_coord = self.decoder.run(memory, mem_kpm, mem_pos, anchor, time_embed)
         fork.join(time_hs, weights)
-        if PREFIX_TRIGGER != "entry":
-            ops.run_deferred()   # (experiment STCAT_PREFIX_TRIGGER=exit: behind the decoders' forward, under their backward)
         return hs, ref, time_hs, weights, pos_query
 
     def forward(self, memory_cache, vis_pos=None, text_cls=None):
@@ -482,9 +314,6 @@ class QueryDecoder(plans.InvalidatesPlans, nn.Module):
                                                 memory_cache["frames_cls"], memory_cache["videos_cls"])
         # reference layouts: hs/ref/time_hs [layers, b, T, *], weights [layers, b, T, T]
         return [hs[:, None], ref[:, None]], (time_hs[:, None], weights)
-
-
-PREFIX_TRIGGER = __import__("os").environ.get("STCAT_PREFIX_TRIGGER", "entry")
 
 
 def build_encoder(cfg=None) -> CrossModalEncoder:

@@ -352,7 +352,7 @@ def _pad8(xs):
 def linear_multi_ok(M: int, N: int, K: int, like: torch.Tensor) -> bool:
     """the grouped skinny-Linear launches apply: a split-bf16 mode, M <= 128, 128-multiples (stcat_linear_wgrad_multi's
     tile, dense leading dimensions), and a source of zeroed outputs"""
-    return (MULTI_LINEAR and L.get_mma_mode() != "f32" and M <= 128 and N % 128 == 0 and K % 128 == 0
+    return (L.get_mma_mode() != "f32" and M <= 128 and N % 128 == 0 and K % 128 == 0
             and (L.RECORDER is not None or _ARENA.get(str(like.device)) is not None))
 
 
@@ -375,9 +375,6 @@ def linear_wgrad_multi(gs, xs, dws, dbs, M, N, K):
     n = len(gs)
     assert 1 <= n <= 8
     L.call("stcat_linear_wgrad_multi", n, *_pad8(gs), *_pad8(xs), *_pad8(dws), *_pad8(dbs), M, N, K, L.stream_of(gs[0]))
-
-
-MULTI_LINEAR = not os.environ.get("STCAT_NO_MULTI_LINEAR")
 
 
 def act_bwd_raw(dy, y, scale, want_g=True, want_res=False, relu=True):
@@ -918,11 +915,34 @@ def _ld3(t: torch.Tensor) -> int:
 # MFMAs per wave — measured +0.25 ms per C3 step (profiles/r05_as_kernel_experiments.log, item 8); it halves the
 # attention's activation memory, which is what it is kept for.
 MHA_RECOMPUTE = bool(os.environ.get("STCAT_MHA_RECOMPUTE"))
-MHA_BS6_MIN_ROWS = int(os.environ.get("STCAT_MHA_BS6_MIN_ROWS", "128"))
-MHA_FP32_PIPE = bool(os.environ.get("STCAT_MHA_FP32_PIPE"))      # A/B switch: every mode's self-attention on the fp32-pipe kernels
+MHA_BS6_MIN_ROWS = 128       # mode bf16x6p: rows up to this length stay on the fp32-pipe kernels (see MhaSelfFn.forward)
 # OPT-IN: gradient-carrying rows of 257..512 tokens on the bf16-pipe kernels as well (no S x S stash, no dS scratch).  Rows
 # above 512 tokens always train there; the default of this band is unchanged (fp32 long-row kernels).
 MHA_BS_LONG = os.environ.get("STCAT_MHA_BS_LONG", "0") not in ("", "0")
+
+
+def _mha_drop(drop_p: float, n: int, device):
+    """(p, seed, offset, base) of the dropout on the attention probabilities (nn.MultiheadAttention(dropout=p) in train
+    mode): `n` counters of the step's dropout stream; p = 0 takes none"""
+    if drop_p > 0.0:
+        return (float(drop_p),) + _dropout_stream.take(n, device)
+    return (0.0, 0, 0, None)
+
+
+def _mha_grads(v, packed_qk: bool):
+    """dq / dk / dv buffers of MhaSelfFn.backward -> (dq, dk, dv, leading dimension of dq and dk, the tuple backward
+    returns); a packed q|k projection gets ONE [B,S,2D] gradient, dq and dk are its column halves"""
+    B, S, D = v.shape
+    if packed_qk:
+        dqk = _empty(v, B, S, 2 * D)
+        dq, dk, ldg_qk = dqk[:, :, :D], dqk[:, :, D:], 2 * D
+    else:
+        dq = _empty(v, B, S, D)
+        dk = _empty(v, B, S, D)
+        ldg_qk = D
+    dv = _empty(v, B, S, D)
+    ret = (dqk, None, dv) if packed_qk else (dq, dk, dv)
+    return dq, dk, dv, ldg_qk, ret + (None,) * 5
 
 
 class MhaSelfFn(Function):
@@ -952,7 +972,9 @@ class MhaSelfFn(Function):
         # For 256 < S <= 512 the DEFAULT stays the fp32 long-row kernels (S x S probability stash + a same-sized dS scratch:
         # 2 x 210 MB per spatial layer at T = 64, S = 310); MHA_BS_LONG sends that band to the bf16-pipe kernels too.
         # (round 6: mode bf16x6p runs here too — three planes per operand, six products: csrc/attention_bs.h, NP = 3; the
-        #  frozen experimental mode f16x3p keeps the fp32-pipe kernels)
+        #  frozen experimental mode f16x3p keeps the fp32-pipe kernels; end to end the two pipes measured the same in that
+        #  mode, 76.41 / 76.56 against 76.34 / 76.57 ms per C3 step, profiles/r06_prefix_pipeline.log box E;
+        #  isolated kernel times: profiles/r06_attention.log)
         # In bf16x6p only rows longer than 128 tokens take the six-product kernels (the encoder's spatial layers: 207 at C3):
         # on the decoders' 64 queries and the temporal layers' 65 rows the fp32-pipe kernels are the faster ones — forward +
         # backward 36.0 vs 42.5 us at S = 64, 45.0 vs 48.5 at S = 65 (isolated, profiles/r06_attention.log: three planes of
@@ -960,22 +982,20 @@ class MhaSelfFn(Function):
         # step's latency-bound chains.
         mode = L.get_mma_mode()
         grads = any(ctx.needs_input_grad[:3])
-        ctx.bs = ((not need_weights) and mode not in ("f32", "f16x3p") and not MHA_FP32_PIPE
+        ctx.bs = ((not need_weights) and mode not in ("f32", "f16x3p")
                   and (mode != "bf16x6p" or S > MHA_BS6_MIN_ROWS)
                   and (S <= 256 or S > 512 or MHA_BS_LONG or not grads))
         if not ctx.bs and S > 512:
             why = ("the head-mean attention weights are wanted" if need_weights else
                    f"mma mode {mode!r}" if mode in ("f32", "f16x3p") else
-                   "STCAT_MHA_FP32_PIPE is set" if MHA_FP32_PIPE else
                    f"MHA_BS6_MIN_ROWS = {MHA_BS6_MIN_ROWS} keeps mode 'bf16x6p' off the bf16 pipe up to that row length")
             raise ValueError(f"mha_self: {S} tokens per row, {why}: this call runs on the fp32-pipe attention kernels, which "
                              "stop at 512 tokens per row; longer rows need mode bf16x3, bf16x3p or bf16x6p and no weights")
+        ctx.rc = False
         if ctx.bs:
             keep = any(ctx.needs_input_grad[:3])
             lse = _empty(v, B, H, S) if keep else None
-            drop = (0.0, 0, 0, None)
-            if drop_p > 0.0:
-                drop = (float(drop_p),) + _dropout_stream.take(B * H * SP * SP, v.device)
+            drop = _mha_drop(drop_p, B * H * SP * SP, v.device)
             L.call("stcat_mha_bs_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), L._ptr(lse),
                    B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
             ctx.drop = drop
@@ -988,9 +1008,7 @@ class MhaSelfFn(Function):
         ctx.rc = (not need_weights) and S <= 256 and MHA_RECOMPUTE and any(ctx.needs_input_grad[:3])
         if ctx.rc:
             lse = _empty(v, B, H, SP, 2)
-            drop = (0.0, 0, 0, None)
-            if drop_p > 0.0:
-                drop = (float(drop_p),) + _dropout_stream.take(B * H * SP * SP, v.device)
+            drop = _mha_drop(drop_p, B * H * SP * SP, v.device)
             L.call("stcat_mha_self_fwd_lse", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), lse.data_ptr(),
                    B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
             ctx.drop = drop
@@ -1000,9 +1018,7 @@ class MhaSelfFn(Function):
         # probabilities are kept only when somebody will read them: backward, or the head-mean weights
         keep = need_weights or any(ctx.needs_input_grad[:3])
         pt = _empty(v, B, H, SP, SP) if keep else None
-        drop = (0.0, 0, 0, None)
-        if drop_p > 0.0:  # dropout on the probabilities (nn.MultiheadAttention(dropout=p) in train mode)
-            drop = (float(drop_p),) + _dropout_stream.take(B * H * SP * SP, v.device)
+        drop = _mha_drop(drop_p, B * H * SP * SP, v.device)
         L.call("stcat_mha_self_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), L._ptr(pt),
                B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
         wts = None
@@ -1019,68 +1035,29 @@ class MhaSelfFn(Function):
 
     @staticmethod
     def backward(ctx, do, dwts):
-        if ctx.bs:
+        do = _c(do)
+        if ctx.bs or ctx.rc:      # both keep the row statistics only and share one argument list
             q, k, v, o, lse, kp = ctx.saved_tensors
             B, S, D = v.shape
             H = D // 32
-            do = _c(do)
-            if ctx.packed_qk:
-                dqk = _empty(v, B, S, 2 * D)
-                dq, dk, ldg_qk = dqk[:, :, :D], dqk[:, :, D:], 2 * D
-            else:
-                dq = _empty(v, B, S, D)
-                dk = _empty(v, B, S, D)
-                ldg_qk = D
-            dv = _empty(v, B, S, D)
-            L.call("stcat_mha_bs_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), do.data_ptr(),
-                   lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S, _ld3(q), _ld3(k), _ld3(v), D,
-                   ldg_qk, D, ctx.scale, *ctx.drop, L.stream_of(v))
-            if ctx.packed_qk:
-                return dqk, None, dv, None, None, None, None, None
-            return dq, dk, dv, None, None, None, None, None
-        if getattr(ctx, "rc", False):
-            q, k, v, o, lse, kp = ctx.saved_tensors
-            B, S, D = v.shape
-            H = D // 32
-            do = _c(do)
-            if ctx.packed_qk:
-                dqk = _empty(v, B, S, 2 * D)
-                dq, dk, ldg_qk = dqk[:, :, :D], dqk[:, :, D:], 2 * D
-            else:
-                dq = _empty(v, B, S, D)
-                dk = _empty(v, B, S, D)
-                ldg_qk = D
-            dv = _empty(v, B, S, D)
-            L.call("stcat_mha_self_bwd_lse", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), do.data_ptr(),
-                   lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S, _ld3(q), _ld3(k), _ld3(v), D,
-                   ldg_qk, D, ctx.scale, *ctx.drop, L.stream_of(v))
-            if ctx.packed_qk:
-                return dqk, None, dv, None, None, None, None, None
-            return dq, dk, dv, None, None, None, None, None
+            dq, dk, dv, ldg_qk, ret = _mha_grads(v, ctx.packed_qk)
+            L.call("stcat_mha_bs_bwd" if ctx.bs else "stcat_mha_self_bwd_lse", q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                   L._ptr(kp), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                   B, H, S, _ld3(q), _ld3(k), _ld3(v), D, ldg_qk, D, ctx.scale, *ctx.drop, L.stream_of(v))
+            return ret
         q, k, v, o, pt = ctx.saved_tensors
         B, S, D = v.shape
         H = D // 32
-        SP = pt.shape[-1]
-        do = _c(do)
         dw = corr = None
         if ctx.need_weights and dwts is not None:
             dw = _c(dwts)
             corr = _empty(v, B, H, S)
         dst = torch.empty_like(pt)
-        if ctx.packed_qk:
-            dqk = _empty(v, B, S, 2 * D)
-            dq, dk, ldg_qk = dqk[:, :, :D], dqk[:, :, D:], 2 * D
-        else:
-            dq = _empty(v, B, S, D)
-            dk = _empty(v, B, S, D)
-            ldg_qk = D
-        dv = _empty(v, B, S, D)
+        dq, dk, dv, ldg_qk, ret = _mha_grads(v, ctx.packed_qk)
         L.call("stcat_mha_self_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(),
                pt.data_ptr(), L._ptr(dw), L._ptr(corr), dst.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
                B, H, S, _ld3(q), _ld3(k), _ld3(v), D, ldg_qk, D, ctx.scale, *ctx.drop, L.stream_of(v))
-        if ctx.packed_qk:
-            return dqk, None, dv, None, None, None, None, None
-        return dq, dk, dv, None, None, None, None, None
+        return ret
 
 
 def mha_self(q, k, v, kpm, scale, need_weights=False, drop_p=0.0):
@@ -1135,58 +1112,6 @@ class AttnQ1Fn(Function):
                g.data_ptr(), dq1.data_ptr(), L._ptr(dq2), dk1.data_ptr(), L._ptr(dk2), dv.data_ptr(), B, H, S, D,
                _ld3(k1), _ld3(v), ctx.scale, *ctx.drop, L.stream_of(v))
         return dq1, dq2, dk1, dk2, dv, None, None, None
-
-
-class SplitColsFn(Function):
-    """[M, n*D] -> n column blocks [M, D] (strided views).  Used to run the K/V projections of all decoder
-    layers as ONE GEMM on the shared memory tensor; the backward concatenates the per-layer gradients so the
-    batched GEMM also has a single dgrad / wgrad."""
-
-    @staticmethod
-    def forward(ctx, x, n):
-        D = x.shape[-1] // n
-        ctx.n, ctx.D = n, D
-        ctx.like = x
-        return tuple(x[..., i * D:(i + 1) * D] for i in range(n))
-
-    @staticmethod
-    def backward(ctx, *gs):
-        x = ctx.like
-        cols = [g if g is not None else torch.zeros(*x.shape[:-1], ctx.D, device=x.device, dtype=x.dtype) for g in gs]
-        return torch.cat(cols, dim=-1), None
-
-
-def split_cols(x, n):
-    return SplitColsFn.apply(x, n)
-
-
-class SplitRowsFn(Function):
-    """Row blocks of a packed parameter (nn.MultiheadAttention's in_proj_weight [3D, D] / in_proj_bias [3D]) as
-    views.  Plain slicing costs, per slice and step, a full-size zero fill + a copy in SliceBackward and an add to
-    merge the slices' gradients (~500 launches per step over the 24 attention layers); here the backward is ONE
-    concatenation of the per-block gradients."""
-
-    @staticmethod
-    def forward(ctx, x, sizes):
-        assert sum(sizes) == x.shape[0]
-        ctx.sizes = sizes
-        ctx.rest = tuple(x.shape[1:])
-        ctx.dev, ctx.dt = x.device, x.dtype
-        out, a = [], 0
-        for n in sizes:
-            out.append(x[a:a + n])
-            a += n
-        return tuple(out)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        parts = [g if g is not None else torch.zeros(n, *ctx.rest, device=ctx.dev, dtype=ctx.dt)
-                 for g, n in zip(gs, ctx.sizes)]
-        return torch.cat(parts, dim=0), None
-
-
-def split_rows(x, sizes):
-    return SplitRowsFn.apply(x, tuple(sizes))
 
 
 def attn_q1(q1, q2, k1, k2, v, kpm, scale, drop_p=0.0):

@@ -71,18 +71,11 @@ class STCATNet(plans.InvalidatesPlans, nn.Module):
     def decode(self, memory, mem_mask, mem_pos, frames_cls, video_cls):
         """pipeline.py:77-103 on tensors only: -> (coord [L,T,4], sted [L,1,T,2], act [L,1,T,1] | None, weights [L,1,T,T])"""
         hs, ref, time_hs, weights, _ = self.ground_decoder.run(memory, mem_mask, mem_pos, frames_cls, video_cls)  # :77-80
-        coord, self.ground_decoder.last_coord = getattr(self.ground_decoder, "last_coord", None), None
-        if coord is None:
-            coord = ops.sigmoid(ops.add(self.bbox_embed(hs), ops.inverse_sigmoid(ref)))      # [L,T,4]  :88-93
-        act = None
-        if composite.ENABLED:
-            sted, act = composite.time_heads(self.temp_embed, self.action_embed if self.use_actioness else None, time_hs)
-            sted = sted[:, None]                                                             # [L,1,T,2]  :98
-            act = act[:, None] if act is not None else None                                  # :103
-        else:
-            sted = self.temp_embed(time_hs)[:, None]
-            if self.use_actioness:
-                act = self.action_embed(time_hs)[:, None]
+        # the box head (:88-93) was evaluated inside the box decoder's node (composite.BoxDecoderFn): coord [L,T,4]
+        coord, self.ground_decoder.last_coord = self.ground_decoder.last_coord, None
+        sted, act = composite.time_heads(self.temp_embed, self.action_embed if self.use_actioness else None, time_hs)
+        sted = sted[:, None]                                                                 # [L,1,T,2]  :98
+        act = act[:, None] if act is not None else None                                      # :103
         return coord, sted, act, weights
 
     def forward(self, videos: NestedTensor, texts, logger=None) -> Dict:

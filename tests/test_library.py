@@ -44,6 +44,26 @@ def test_no_cpu_fallback():
         ops.linear(torch.zeros(4, 64), torch.zeros(64, 64), torch.zeros(64))
 
 
+def test_environment_variables_are_documented():
+    """every STCAT_* variable the package reads — os.environ in stcat_amd/*.py, getenv in stcat_amd/csrc/* — has its row in
+    INTEGRATION.md's table (name, default, effect, user-facing or debug): an undocumented switch cannot be added"""
+    read = {}
+    pkg = os.path.join(ROOT, "stcat_amd")
+    for sub, pattern in (("", r"os\.environ(?:\.get\(|\[)\s*[\"'](STCAT_[A-Z0-9_]+)[\"']"),
+                         ("csrc", r"\bgetenv\(\s*\"(STCAT_[A-Z0-9_]+)\"")):
+        d = os.path.join(pkg, sub)
+        for fn in sorted(os.listdir(d)):
+            path = os.path.join(d, fn)
+            if os.path.isfile(path) and (sub or fn.endswith(".py")):
+                for name in re.findall(pattern, open(path, errors="replace").read()):
+                    read.setdefault(name, os.path.relpath(path, ROOT))
+    assert "STCAT_DETERMINISTIC" in read and "STCAT_PLANS" in read, read      # (the scan itself finds both languages' reads)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    documented = set(re.findall(r"STCAT_[A-Z0-9_]+", doc))
+    missing = {name: where for name, where in read.items() if name not in documented}
+    assert not missing, f"read by the package, absent from INTEGRATION.md: {missing}"
+
+
 @pytest.mark.gpu
 def test_gpu_side_streams_run_beside_the_current_stream():
     """ops._pick_streams: the side stream (forward chains / forked decoder) and the weight-gradient stream it returns sit

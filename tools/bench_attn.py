@@ -34,7 +34,7 @@ with torch.no_grad():
     t_inf = timeit(lambda: ops.mha_self_packed(qk.detach(), v.detach(), kpm, 32 ** -0.5)[0])
 print(f"S={S}: inference fwd (no probability stash) {t_inf*1e3:.1f} us = {fl/t_inf/1e9:.1f} TF")
 # the routes of a call with gradients: one outside the 257..512 band (or where the mode keeps the fp32-pipe kernels anyway)
-two = 256 < S <= 512 and L.get_mma_mode() not in ("f32", "f16x3p") and not ops.MHA_FP32_PIPE
+two = 256 < S <= 512 and L.get_mma_mode() not in ("f32", "f16x3p")
 routes = [("fp32 long-row (default)", False), ("bf16 pipe (MHA_BS_LONG)", True)] if two else [("", None)]
 for rep in range(int(os.environ.get("ROUNDS", "3")) if two else 1):
     for name, flag in routes:

@@ -23,9 +23,8 @@ P='import json,sys; d=json.loads(sys.stdin.readline()); print({k:d.get(k) for k 
   timeout 300 $B --steps 10 --warmup 3 --no-profile --serial 2>&1 | tail -1 | python -c "$P"
   timeout 300 $B --steps 10 --warmup 3 --no-profile --hoist-loss-plan 2>&1 | tail -1 | python -c "$P"
   timeout 300 $B --steps 10 --warmup 3 --no-profile --no-auto-graph --config C1 2>&1 | tail -1 | python -c "$P"
-  echo "# round 6: --no-prefix-pipeline (every step computes its clip's frozen prefix itself) | STCAT_MHA_FP32_PIPE=1 (self-attention on the fp32-pipe kernels of round 5) | default again"
+  echo "# round 6: --no-prefix-pipeline (every step computes its clip's frozen prefix itself) | default again"
   timeout 300 $B --steps 10 --warmup 3 --no-profile --no-prefix-pipeline 2>&1 | tail -1 | python -c "$P"
-  STCAT_MHA_FP32_PIPE=1 timeout 300 $B --steps 10 --warmup 3 --no-profile 2>&1 | tail -1 | python -c "$P"
   timeout 300 $B --steps 10 --warmup 3 --no-profile 2>&1 | tail -1 | python -c "$P"
 } > $O/bench_variants.log 2>&1; cat $O/bench_variants.log
 # host profile of the bench mode with launch plans ON: the untraced node timeline (events between the autograd nodes of the
