@@ -45,8 +45,9 @@ int stcat_get_f16_scale(int which);
  * device's CU count, never by arrival order, so equal inputs give equal bits run to run.  An entry point that has no
  * ordered form for a call FAILS (-1, stcat_last_error() names it and what it needs) instead of falling back to a float
  * atomic: stcat_pl_conv_wgrad[_ws] without / with too small a workspace when its reduction is split, stcat_grad_sqnorm
- * over more than one chunk (use stcat_grad_sqnorm_ws), stcat_map2d_*_bwd, stcat_debug_pl_flags bit 0x4000.  Off: nothing
- * changes.  Not stream-ordered (host state, like the mma mode); every mma mode is supported. */
+ * over more than one chunk (use stcat_grad_sqnorm_ws), the scatter entries stcat_map2d_cells_bwd / stcat_map2d_pool_bwd
+ * (use their _gather forms, as the 2D-map head does), stcat_debug_pl_flags bit 0x4000.  Off: nothing changes.
+ * Not stream-ordered (host state, like the mma mode); every mma mode is supported. */
 int stcat_set_deterministic(int on);
 int stcat_get_deterministic(void);
 /* tuning/test hook: force the implicit-GEMM block tile (128x128, 128x64, 64x64; 0,0 = heuristic) */
@@ -369,8 +370,18 @@ int stcat_map2d_cells(const float* pooled, const int* cell_i, const int* cell_j,
 int stcat_map2d_cells_bwd(const float* pooled, const int* cell_i, const int* cell_j, int ncells, const float* dmap,
                           float* dpooled, int b, int N, int D, void* stream);
 int stcat_map2d_pool_bwd(const float* x, const float* dpooled, float* dx, int b, int T, int N, int D, void* stream);
+/* the same two gradients (map2d_head.py:48-61 backwards) in GATHER form: one writer per element of dpooled / dx, the
+ * contributions added in ascending cell / pooled-step order — no atomics, the outputs need not be zeroed.  A cell's
+ * gradient still goes to the first maximum of its range, a T <= N window's to its first maximum.  arg_ws: workspace of
+ * b * ncells * D ints (the first-maximum step per cell and channel).  The form the deterministic mode uses. */
+int stcat_map2d_cells_bwd_gather(const float* pooled, const int* cell_i, const int* cell_j, int ncells, const float* dmap,
+                                 int* arg_ws, float* dpooled, int b, int N, int D, void* stream);
+int stcat_map2d_pool_bwd_gather(const float* x, const float* dpooled, float* dx, int b, int T, int N, int D, void* stream);
 /* y[m, :] *= w[m % period]: the per-pixel mask-normalisation weight after each conv + ReLU (:247-249) */
 int stcat_rowscale(float* y, const float* w, long rows, int C, int period, void* stream);
+/* stcat_rowscale on a plane set [rows][C] in place (:247-249 with the map kept as planes): join, multiply in fp32,
+ * re-split; C % 8 == 0; plane modes only */
+int stcat_pl_rowscale(void* h, void* l, const float* w, long rows, int C, int period, void* stream);
 
 /* ---- VideoSTGLoss (models/criterion.py:11-208), all decoder layers in one launch --------------------------------
  * vec[k*nl + l] = un-weighted loss k of decoder layer l; k = 0 loss_bbox (criterion.py:38-55), 1 loss_giou (:56-66),

@@ -65,7 +65,10 @@ SIGNATURES: Dict[str, str] = {
     "stcat_map2d_cells": "pppipiiis",
     "stcat_map2d_cells_bwd": "pppippiiis",
     "stcat_map2d_pool_bwd": "pppiiiis",
+    "stcat_map2d_cells_bwd_gather": "pppipppiiis",
+    "stcat_map2d_pool_bwd_gather": "pppiiiis",
     "stcat_rowscale": "pplii" + "s",
+    "stcat_pl_rowscale": "ppplii" + "s",
     "stcat_grad_sqnorm": "pppiips",
     "stcat_grad_sqnorm_ws": "pppiippls",
     "stcat_adamw_ema_step": "pppiipPPifffiffs",

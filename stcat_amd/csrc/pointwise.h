@@ -620,6 +620,90 @@ __global__ void __launch_bounds__(256) map2d_pool_bwd_kernel(const float* x, con
   }
 }
 
+// Gather forms of the two backward kernels above (deterministic mode): ONE writer per output element, contributions added
+// in ascending cell / pooled-step order, no atomics and no caller-zeroed outputs.  Pass 1 stores, per (batch, cell,
+// channel), the step of the FIRST maximum of the cell's range (what the scatter kernel computes before its atomicAdd).
+__global__ void __launch_bounds__(256) map2d_cells_arg_kernel(const float* pooled, const int* ci, const int* cj, int ncells,
+                                                             int* arg_out, int b, int N, int D) {
+  const long total = (long)b * ncells * D;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int d = (int)(i % D), c = (int)((i / D) % ncells), bb = (int)(i / ((long)D * ncells));
+    const int i0 = ci[c], j0 = cj[c];
+    const float* src = pooled + ((long)bb * N) * D + d;
+    float best = src[(long)i0 * D];
+    int arg = i0;
+    for (int n = i0 + 1; n <= j0; ++n) {
+      const float v = src[(long)n * D];
+      if (v > best) { best = v; arg = n; }
+    }
+    arg_out[i] = arg;
+  }
+}
+// Pass 2: dpooled[bb][n][d] = sum over the cells c (ascending) whose range holds n and whose first maximum is n
+__global__ void __launch_bounds__(256) map2d_cells_bwd_gather_kernel(const int* arg, const int* ci, const int* cj, int ncells,
+                                                                    const float* dmap, float* dpooled, int b, int N, int D) {
+  const long total = (long)b * N * D;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int d = (int)(i % D), n = (int)((i / D) % N), bb = (int)(i / ((long)D * N));
+    float acc = 0.f;
+    for (int c = 0; c < ncells; ++c) {
+      const int i0 = ci[c], j0 = cj[c];
+      if (n < i0 || n > j0) continue;
+      if (arg[((long)bb * ncells + c) * D + d] == n) acc += dmap[(((long)bb * N + i0) * N + j0) * D + d];
+    }
+    dpooled[i] = acc;
+  }
+}
+// dx[bb][t][d] = sum over the pooled steps n (ascending) whose window [floor(n T / N), ceil((n+1) T / N)) holds t:
+// T > N: dpooled / window length; T <= N: dpooled where t is the first maximum of the window.
+// floor(n T / N) <= t < ceil((n+1) T / N)  <=>  t N / T - 1 < n < (t+1) N / T
+__global__ void __launch_bounds__(256) map2d_pool_bwd_gather_kernel(const float* x, const float* dpooled, float* dx, int b,
+                                                                   int T, int N, int D) {
+  const long total = (long)b * T * D;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int d = (int)(i % D), t = (int)((i / D) % T), bb = (int)(i / ((long)D * T));
+    const int n_lo = (int)(((long)t * N) / T);
+    int n_hi = (int)((((long)t + 1) * N + T - 1) / T) - 1;
+    if (n_hi > N - 1) n_hi = N - 1;
+    const float* src = x + ((long)bb * T) * D + d;
+    float acc = 0.f;
+    for (int n = n_lo; n <= n_hi; ++n) {
+      const int s = (int)(((long)n * T) / N), e = (int)((((long)n + 1) * T + N - 1) / N);
+      if (t < s || t >= e) continue;
+      const float g = dpooled[((long)bb * N + n) * D + d];
+      if (T > N) {
+        acc += g / (float)(e - s);
+      } else {
+        float best = src[(long)s * D];
+        int arg = s;
+        for (int u = s + 1; u < e; ++u) {
+          const float v = src[(long)u * D];
+          if (v > best) { best = v; arg = u; }
+        }
+        if (arg == t) acc += g;
+      }
+    }
+    dx[i] = acc;
+  }
+}
+
+// rowscale_kernel (below) on a plane set [rows][C] (C % 8 == 0), in place: join, multiply in fp32, re-split.  Three
+// planes hold any fp32 value, so in mode bf16x6p the result is the fp32 product exactly.
+__global__ void __launch_bounds__(256) pl_rowscale_kernel(__bf16* h, __bf16* l, const float* w, long rows, int C, int period,
+                                                         int np) {
+  const int c8n = C / 8;
+  const long total = rows * c8n;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long m = i / c8n;
+    const float f = w[m % period];
+    float v[8];
+    stcat_load_planes(h, l, i * 8, np, v);
+    STCAT_UNROLL
+    for (int e = 0; e < 8; ++e) v[e] *= f;
+    stcat_store_planes(v, h, l, i * 8, np);
+  }
+}
+
 // y[m][:] *= w[m % period]  — the mask-normalisation weight of TempConvInteraction (:245-249): one factor per map pixel
 __global__ void __launch_bounds__(256) rowscale_kernel(float* y, const float* w, long rows, int C, int period) {
   const int c4n = C / 4;

@@ -1943,7 +1943,7 @@ int stcat_map2d_cells(const float* pooled, const int* cell_i, const int* cell_j,
 int stcat_map2d_cells_bwd(const float* pooled, const int* cell_i, const int* cell_j, int ncells, const float* dmap,
                           float* dpooled, int b, int N, int D, void* stream) {
   if (ncells <= 0 || b <= 0 || N <= 0 || D <= 0) return fail("map2d_cells_bwd: bad shape");
-  if (g_deterministic) return det_refuse("map2d_cells_bwd", "the 2D-map head's backward scatters with float atomics and has no ordered form");
+  if (g_deterministic) return det_refuse("map2d_cells_bwd", "this entry scatters with float atomics; the ordered form is stcat_map2d_cells_bwd_gather");
   STCAT_LAUNCH(map2d_cells_bwd_kernel, dim3(grid_for((long)b * ncells * D, 256)), dim3(256), 0, (hipStream_t)stream, pooled,
                cell_i, cell_j, ncells, dmap, dpooled, b, N, D);
   return launch_status();
@@ -1951,7 +1951,7 @@ int stcat_map2d_cells_bwd(const float* pooled, const int* cell_i, const int* cel
 
 int stcat_map2d_pool_bwd(const float* x, const float* dpooled, float* dx, int b, int T, int N, int D, void* stream) {
   if (b <= 0 || T <= 0 || N <= 0 || D <= 0) return fail("map2d_pool_bwd: bad shape");
-  if (g_deterministic) return det_refuse("map2d_pool_bwd", "the 2D-map head's backward scatters with float atomics and has no ordered form");
+  if (g_deterministic) return det_refuse("map2d_pool_bwd", "this entry scatters with float atomics; the ordered form is stcat_map2d_pool_bwd_gather");
   STCAT_LAUNCH(map2d_pool_bwd_kernel, dim3(grid_for((long)b * N * D, 256)), dim3(256), 0, (hipStream_t)stream, x, dpooled, dx,
                b, T, N, D);
   return launch_status();
@@ -1960,6 +1960,38 @@ int stcat_map2d_pool_bwd(const float* x, const float* dpooled, float* dx, int b,
 int stcat_rowscale(float* y, const float* w, long rows, int C, int period, void* stream) {
   if (C % 4 != 0 || rows <= 0 || period <= 0) return fail("rowscale: bad shape");
   STCAT_LAUNCH(rowscale_kernel, dim3(grid_for(rows * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, y, w, rows, C, period);
+  return launch_status();
+}
+
+// gather forms of the two backward entries (one writer per element, ascending order: what the deterministic mode runs)
+int stcat_map2d_cells_bwd_gather(const float* pooled, const int* cell_i, const int* cell_j, int ncells, const float* dmap,
+                                 int* arg_ws, float* dpooled, int b, int N, int D, void* stream) {
+  if (ncells <= 0 || b <= 0 || N <= 0 || D <= 0) return fail("map2d_cells_bwd_gather: bad shape");
+  if (!pooled || !cell_i || !cell_j || !dmap || !dpooled) return fail("map2d_cells_bwd_gather: pooled, the cell lists, dmap and dpooled are required");
+  if (!arg_ws) return fail("map2d_cells_bwd_gather: needs a workspace of b x ncells x D ints");
+  STCAT_LAUNCH(map2d_cells_arg_kernel, dim3(grid_for((long)b * ncells * D, 256)), dim3(256), 0, (hipStream_t)stream, pooled,
+               cell_i, cell_j, ncells, arg_ws, b, N, D);
+  if (int rc = launch_status()) return rc;
+  STCAT_LAUNCH(map2d_cells_bwd_gather_kernel, dim3(grid_for((long)b * N * D, 256)), dim3(256), 0, (hipStream_t)stream,
+               (const int*)arg_ws, cell_i, cell_j, ncells, dmap, dpooled, b, N, D);
+  return launch_status();
+}
+
+int stcat_map2d_pool_bwd_gather(const float* x, const float* dpooled, float* dx, int b, int T, int N, int D, void* stream) {
+  if (b <= 0 || T <= 0 || N <= 0 || D <= 0) return fail("map2d_pool_bwd_gather: bad shape");
+  if (!x || !dpooled || !dx) return fail("map2d_pool_bwd_gather: x, dpooled and dx are required");
+  STCAT_LAUNCH(map2d_pool_bwd_gather_kernel, dim3(grid_for((long)b * T * D, 256)), dim3(256), 0, (hipStream_t)stream, x,
+               dpooled, dx, b, T, N, D);
+  return launch_status();
+}
+
+int stcat_pl_rowscale(void* h, void* l, const float* w, long rows, int C, int period, void* stream) {
+  if (C <= 0 || C % 8 != 0 || rows <= 0 || period <= 0) return fail("pl_rowscale: bad shape (C %% 8 == 0)");
+  if (!h || !l || !w) return fail("pl_rowscale: the plane pair and w are required");
+  if (!aligned16(h) || !aligned16(l)) return fail("pl_rowscale: planes must be 16-byte aligned");
+  if (g_mma_mode_raw < 4) return fail("pl_rowscale: plane modes only");
+  STCAT_LAUNCH(pl_rowscale_kernel, dim3(grid_for(rows * (C / 8), 256, 8192)), dim3(256), 0, (hipStream_t)stream, (__bf16*)h,
+               (__bf16*)l, w, rows, C, period, pl_np_arg());
   return launch_status();
 }
 
@@ -2040,6 +2072,9 @@ const stcat_plan::FnEntry g_plan_fns[] = {
     STCAT_PLAN_FN(stcat_pl_act_bwd),
     STCAT_PLAN_FN(stcat_pl_scale),
     STCAT_PLAN_FN(stcat_weight_planes_multi),
+    STCAT_PLAN_FN(stcat_map2d_cells_bwd_gather),
+    STCAT_PLAN_FN(stcat_map2d_pool_bwd_gather),
+    STCAT_PLAN_FN(stcat_pl_rowscale),
 };
 constexpr int kPlanFns = (int)(sizeof(g_plan_fns) / sizeof(g_plan_fns[0]));
 inline stcat_plan::Plan* plan_of(void* h) { return static_cast<stcat_plan::Plan*>(h); }

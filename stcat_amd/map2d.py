@@ -12,6 +12,10 @@ from the imported reference (tests/golden/map2d.npz).  Not part of the videos/se
 * TempConvInteraction: k x k convolutions (bias, ReLU) through the implicit-GEMM kernels of the backbone (forward, data
   gradient, weight gradient), each followed by the per-pixel mask-normalisation weight; the 1x1 predictor is the
   small-N linear kernel; eval applies sigmoid * mask2d.
+  `TempPredictionHead(planes=True)` (opt-in, modes bf16x6p / bf16x3p) runs the same stack on the bf16 plane pipeline
+  (`_ConvStackPlanesFn`): the map is split once and stays planes until the predictor; 77.6 ms instead of 104.9 ms forward +
+  backward at the reference size (tools/bench_map2d.py, profiles/map2d_planes.log).
+* deterministic mode: Gen2DMap's backward switches from the scatter kernels (float atomics) to their gather forms.
 * 'attn': per map, `TEMP_PRED_LAYERS` post-norm layers of attention along the rows (batched over the columns), then
   along the columns (batched over the rows), FFN.  The reference passes `mask2d` (True = VALID cell) as
   `key_padding_mask` (True = ignore, :171-183): the valid cells are the ones masked out.  Mirrored as is.
@@ -73,6 +77,16 @@ class _Gen2DMapFn(Function):
         N = ctx.N
         dmap = dmap.contiguous()
         st = L.stream_of(dmap)
+        if L.is_deterministic():
+            # gather forms: one writer per element, contributions in ascending cell / step order (no atomics, no zeroing)
+            ncells = int(cell_i.numel())
+            arg = torch.empty(b, ncells, D, device=x.device, dtype=torch.int32)
+            dpooled = torch.empty_like(pooled)
+            L.call("stcat_map2d_cells_bwd_gather", pooled.data_ptr(), cell_i.data_ptr(), cell_j.data_ptr(), ncells,
+                   dmap.data_ptr(), arg.data_ptr(), dpooled.data_ptr(), b, N, D, st)
+            dx = torch.empty_like(x)
+            L.call("stcat_map2d_pool_bwd_gather", x.data_ptr(), dpooled.data_ptr(), dx.data_ptr(), b, T, N, D, st)
+            return dx, None, None, None
         dpooled = torch.zeros_like(pooled)
         L.call("stcat_map2d_cells_bwd", pooled.data_ptr(), cell_i.data_ptr(), cell_j.data_ptr(), int(cell_i.numel()),
                dmap.data_ptr(), dpooled.data_ptr(), b, N, D, st)
@@ -121,6 +135,61 @@ class _ConvReluScaleFn(Function):
         dw = ops.conv_wgrad_raw(g, x, w_ohwi.shape, 1, ctx.pad).permute(0, 3, 1, 2) if ctx.needs_input_grad[1] else None
         db = ops.colsum(g.view(-1, g.shape[-1])) if ctx.needs_input_grad[2] else None
         return dx, dw, db, None, None
+
+
+class _ConvStackPlanesFn(Function):
+    """The whole of TempConvInteraction (map2d_head.py:245-249) on the bf16 plane pipeline: the fp32 NHWC map is split
+    once and stays planes until the last layer, whose output is fp32 for the predictor.  Per layer: plane conv (bias, ReLU,
+    bit mask from the epilogue) + the per-pixel weight on planes.  Backward per layer from the top: g_i = upstream * w_i *
+    [y_i > 0] as planes (from fp32 through pl_act_bwd, between layers through the data gradient's bit-mask epilogue — w >= 0,
+    so masking and row scaling commute, and where w = 0 the gradient is zero whatever the mask says), plane weight
+    gradient, pl_colsum for the bias."""
+
+    @staticmethod
+    def forward(ctx, m, head, *params):
+        n_layers = head.n
+        ws, bs = params[:n_layers], params[n_layers:]
+        fwd, tr = head._weight_planes(ws)
+        x = ops.pl_split(m)
+        xs, y = [], None
+        for i in range(n_layers):
+            pix_w = getattr(head, f"weight{i}")
+            last = i == n_layers - 1
+            xs.append(x)
+            yp, y = ops.pl_conv_fwd_raw(x, fwd[i], None, bs[i], None, 1, head.pad0 if i == 0 else 0, True,
+                                        planes_out=not last, f32_out=last, want_mask=True)
+            if last:
+                L.call("stcat_rowscale", y.data_ptr(), pix_w.data_ptr(), y.shape[0] * y.shape[1] * y.shape[2], y.shape[3],
+                       pix_w.numel(), L.stream_of(y))
+            else:
+                x = ops.pl_rowscale(yp, pix_w)
+        ctx.head, ctx.xs, ctx.tr = head, xs, tr
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        head, xs, tr = ctx.head, ctx.xs, ctx.tr
+        y, = ctx.saved_tensors
+        n_layers, k = head.n, head.k
+        # the pixel weight is >= 0 and y carries it: y > 0 <=> relu(...) > 0 wherever the weight is not zero
+        g, _ = ops.pl_act_bwd_raw(dy, y, None, want_g=True, relu=True)
+        ops.pl_rowscale(g, getattr(head, f"weight{n_layers - 1}"))
+        dws, dbs, dm = [None] * n_layers, [None] * n_layers, None
+        for i in range(n_layers - 1, -1, -1):
+            x, pad = xs[i], head.pad0 if i == 0 else 0
+            C = g.shape[-1]
+            if ctx.needs_input_grad[2 + i]:
+                dws[i] = ops.pl_conv_wgrad_raw(g, x, (C, k, k, x.shape[-1]), 1, pad).permute(0, 3, 1, 2)
+            if ctx.needs_input_grad[2 + n_layers + i]:
+                dbs[i] = ops.pl_colsum(ops.Planes(g.t.view(g.t.shape[0], -1, C)))
+            if i > 0:
+                # x = the scaled output of layer i - 1 and carries that layer's ReLU bit mask
+                g = ops.pl_conv_dgrad_raw(g, tr[i], x.shape, k, 1, pad, mask_y=x)
+                ops.pl_rowscale(g, getattr(head, f"weight{i - 1}"))
+            elif ctx.needs_input_grad[0]:
+                dm = ops.pl_join(ops.pl_conv_dgrad_raw(g, tr[i], x.shape, k, 1, pad))
+        return (dm, None, *dws, *dbs)
 
 
 class _ConvStack(nn.Module):
@@ -182,8 +251,15 @@ class TempPredictionHead(nn.Module):
 
     def __init__(self, d_model: int = 256, map_size: int = 128, pooling_counts: Sequence[int] = (15, 8, 8, 8),
                  kernel_size: int = 9, conv_layers: int = 4, temp_head: str = "conv", nhead: int = 8,
-                 dim_feedforward: int = 2048, dropout: float = 0.1, attn_layers: int = 2):
+                 dim_feedforward: int = 2048, dropout: float = 0.1, attn_layers: int = 2, planes: bool = False):
+        """planes=True: the conv interaction runs on the bf16 plane pipeline (mma mode bf16x6p or bf16x3p at call time) —
+        opt-in; the default is the fp32-tensor path."""
         super().__init__()
+        if planes and temp_head != "conv":
+            raise ValueError(f"planes=True needs temp_head='conv' (got {temp_head!r}): only the conv interaction has a plane form")
+        if planes and d_model % 128 != 0:
+            raise ValueError(f"planes=True needs d_model % 128 == 0 (the plane weight gradient's tile), got d_model={d_model}")
+        self.planes = planes
         self.map_maker = Gen2DMap(map_size, pooling_counts)
         self.temp_head = temp_head
         if temp_head == "attn":
@@ -204,6 +280,40 @@ class TempPredictionHead(nn.Module):
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)       # _reset_parameters (:100-103) runs before the predictor exists
         self.predictor = nn.Conv2d(d_model, 1, 1)
+        # plane path: one weight-plane cache for the conv stack, fed from PERSISTENT OHWI copies of the OIHW parameters
+        # (plain attributes: the state dict keeps the reference's names).  A fresh permute().contiguous() per call would
+        # change data_ptr, rebuild the table every step and invalidate the launch plans of the main model.
+        self._wplanes = ops.WeightPlanes() if planes else None
+        self._w_ohwi: List[torch.Tensor] = []
+        self._w_state = None
+
+    def _weight_planes(self, ws):
+        """([fwd planes per layer], [transposed planes per layer]) of the conv weights: the staging copies are rewritten
+        only when a parameter changed (tensor versions + the fused optimizer's epoch), then ONE weight-plane launch.
+        Under a hipGraph capture the copies are always issued, so that they are part of the graph and a replay after an
+        optimizer step re-reads the parameters (WeightPlanes.refresh re-launches under a capture for the same reason); the
+        buffers themselves must exist by then (one eager call first).  A launch-plan recording cannot hold the copy (a
+        torch op, not an entry point of the library): the plane head refuses to be recorded instead of replaying stale
+        weights."""
+        if L.RECORDER is not None:
+            raise L.StcatHipError("TempPredictionHead(planes=True) cannot be recorded into a launch plan: the OHWI staging "
+                                  "copy of its conv weights is not a library launch; call the head outside the recorded scope")
+        capturing = ws[0].is_cuda and torch.cuda.is_current_stream_capturing()
+        if len(self._w_ohwi) != len(ws) or any(s.device != w.device for s, w in zip(self._w_ohwi, ws)):
+            if capturing:
+                raise L.StcatHipError("TempPredictionHead(planes=True): run one eager forward before a graph capture (the "
+                                      "persistent weight staging buffers cannot be allocated inside a capture)")
+            self._w_ohwi = [torch.empty(w.shape[0], w.shape[2], w.shape[3], w.shape[1], device=w.device, dtype=torch.float32)
+                            for w in ws]
+            self._w_state = None
+        state = (ops.WEIGHT_EPOCH, tuple(w._version for w in ws), tuple(w.data_ptr() for w in ws))
+        if state != self._w_state or capturing:
+            with torch.no_grad():
+                for s, w in zip(self._w_ohwi, ws):
+                    s.copy_(w.detach().permute(0, 2, 3, 1))
+            self._w_state = state
+        fwd, tr = self._wplanes.refresh(self._w_ohwi, transposed=True)
+        return [fwd[s.data_ptr()] for s in self._w_ohwi], [tr[s.data_ptr()] for s in self._w_ohwi]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         nl, b, T, D = x.shape
@@ -217,6 +327,13 @@ class TempPredictionHead(nn.Module):
                     mi = layer.run(mi, self.map_maker.mask2d)
                 maps.append(mi)
             m = torch.stack(maps)
+        elif self.planes:
+            mode = L.get_mma_mode()
+            if mode not in ("bf16x6p", "bf16x3p"):
+                raise ValueError(f"TempPredictionHead(planes=True) runs in mma mode 'bf16x6p' or 'bf16x3p', not {mode!r} "
+                                 "(f16x3p: its gradient planes carry a loss scale this head has no policy for)")
+            convs = self.encoder.convs
+            m = _ConvStackPlanesFn.apply(m, self, *[c.weight for c in convs], *[c.bias for c in convs])
         else:
             for i, conv in enumerate(self.encoder.convs):
                 m = _ConvReluScaleFn.apply(m, conv.weight, conv.bias, getattr(self, f"weight{i}"),

@@ -1581,6 +1581,16 @@ def pl_scale_raw(x: Planes, scale: torch.Tensor) -> Planes:
     return out
 
 
+def pl_rowscale(p: Planes, w: torch.Tensor) -> Planes:
+    """IN PLACE: p[m, :] *= w[m % w.numel()] over the rows m of a plane set [..., C] (the 2D-map head's per-pixel weight,
+    map2d_head.py:247-249); the bit mask the planes carry stays valid for w >= 0"""
+    C = p.shape[-1]
+    _chk(w)
+    assert w.dtype == _f32 and w.is_contiguous()
+    L.call("stcat_pl_rowscale", p.h, p.l, w.data_ptr(), p.numel() // C, C, w.numel(), L.stream_of(p.t))
+    return p
+
+
 class WeightPlanes:
     """bf16 hi/lo planes of a fixed list of conv weights, refreshed with ONE launch: forward planes [Cout,KH,KW,Cin]
     and (when `transposed`) the data-gradient operand [taps,Cin,Cout].  Buffers and the device table are persistent;
