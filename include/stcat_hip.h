@@ -25,6 +25,17 @@ extern "C" {
 
 int stcat_version(void);
 const char* stcat_last_error(void);
+/* The library describes its own ABI: entry i of stcat_entry_count() has the name stcat_entry_name(i) and one kind letter
+ * per argument in stcat_entry_kinds(i) (NULL when i is out of range) —
+ *   p device pointer   P host pointer   s stream (void*, always last)   S C string
+ *   i int              l long           f float                         u unsigned long long
+ * Every function below is in the table (these three, stcat_version and stcat_last_error are not); all return int except
+ * stcat_plan_create (void*).  The letters are checked against the C types when the library is compiled
+ * (stcat_amd/csrc/entry_points.h), so a host in any language can build its argument types from the table instead of
+ * typing them again (INTEGRATION.md shows the ctypes loop). */
+int stcat_entry_count(void);
+const char* stcat_entry_name(int i);
+const char* stcat_entry_kinds(int i);
 /* arithmetic of the implicit-GEMM family (conv / Linear fwd, dgrad, wgrad); inputs and outputs stay fp32:
  *   0 = fp32 MFMA (v_mfma_f32_32x32x2_f32, exact fp32 products)
  *   2 = split-bf16 x3: x = hi + lo in bf16, hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16, fp32 accumulate

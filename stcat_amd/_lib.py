@@ -16,109 +16,9 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libstcat_hip.so")
 
-# name -> argument kinds: p = device pointer, i = int, l = long, f = float, s = stream (void*)
-SIGNATURES: Dict[str, str] = {
-    "stcat_frozen_bn_fold": "ppppppifs",
-    "stcat_stem_fwd": "pppppiiis",
-    "stcat_stem_u8_fwd": "pppppppiiis",
-    "stcat_maxpool3x3s2": "ppiiiis",
-    "stcat_conv_fwd": "ppppppiiiiiiiiiis",
-    "stcat_conv_dgrad": "pppppppppiiiiiiiiis",
-    "stcat_weight_transpose": "ppiiis",
-    "stcat_weight_transpose_multi": "piis",
-    "stcat_weight_transpose_entry_bytes": "",
-    "stcat_conv_wgrad": "pppiiiiiiiiis",
-    "stcat_act_bwd": "ppppplii" + "s",
-    "stcat_pos_sine_2d": "pppiiis",
-    "stcat_sine_embed_fwd": "pppis",
-    "stcat_sine_embed_bwd": "ppppis",
-    "stcat_linear_fwd": "pppppiiiiiiiils",
-    "stcat_linear_dgrad": "pppppiiiiis",
-    "stcat_linear_fwd_acc": "pppppiiiiiis",
-    "stcat_linear_dgrad_acc": "ppppiiiiis",
-    "stcat_linear_fwd_multi": "i" + "p" * 32 + "iii" + "s",
-    "stcat_linear_dgrad_multi": "i" + "p" * 32 + "iii" + "s",
-    "stcat_linear_wgrad_multi": "i" + "p" * 32 + "iii" + "s",
-    "stcat_linear_fwd_drop": "ppppp" + "iiiiiii" + "fllp" + "s",
-    "stcat_linear_dgrad_mask": "ppppp" + "f" + "p" + "iiiii" + "s",
-    "stcat_linear_wgrad": "ppppiiiiis",
-    "stcat_small_linear_fwd": "ppppiiis",
-    "stcat_small_linear_bwd": "ppppppiiis",
-    "stcat_colsum": "pppiis",
-    "stcat_layernorm_fwd": "pppppppiif" + "fllps",
-    "stcat_layernorm_bwd": "ppppppppppii" + "fllps",
-    "stcat_ew": "ipppp" + "llffs",
-    "stcat_ew2d": "iplplpllif" + "fs",
-    "stcat_stg_loss_fwd": "p" * 13 + "f" + "iiiii" + "ppp" + "s",
-    "stcat_stg_loss_bwd": "p" * 13 + "f" + "iiiii" + "ppp" + "pppp" + "s",
-    "stcat_dropout": "ppplfllps",
-    "stcat_mha_self_fwd": "ppppppiiiiiiif" + "fllps",
-    "stcat_mha_self_bwd": "pppppppppppp" + "iiiiiiiiif" + "fllps",
-    "stcat_mha_self_fwd_lse": "pppppp" + "iiiiiiif" + "fllps",
-    "stcat_mha_self_bwd_lse": "pppppppppp" + "iiiiiiiiif" + "fllps",
-    "stcat_mha_bs_fwd": "pppppp" + "iiiiiiif" + "fllps",
-    "stcat_mha_bs_bwd": "pppppppppp" + "iiiiiiiiif" + "fllps",
-    "stcat_attn_weights_mean": "ppiii" + "fllps",
-    "stcat_attn_q1_fwd": "pppppppp" + "iiiiiif" + "fllps",
-    "stcat_attn_q1_bwd": "pppppppppppp" + "iiiiiif" + "fllps",
-    "stcat_map2d_pool": "ppiiiis",
-    "stcat_map2d_cells": "pppipiiis",
-    "stcat_map2d_cells_bwd": "pppippiiis",
-    "stcat_map2d_pool_bwd": "pppiiiis",
-    "stcat_map2d_cells_bwd_gather": "pppipppiiis",
-    "stcat_map2d_pool_bwd_gather": "pppiiiis",
-    "stcat_rowscale": "pplii" + "s",
-    "stcat_pl_rowscale": "ppplii" + "s",
-    "stcat_grad_sqnorm": "pppiips",
-    "stcat_grad_sqnorm_ws": "pppiippls",
-    "stcat_adamw_ema_step": "pppiipPPifffiffs",
-    "stcat_grad_clip_scale": "pppiipfs",
-    "stcat_ema_update": "pppiifs",
-    "stcat_optim_table_entry_bytes": "",
-    "stcat_temporal_map_argmax": "pppiis",
-    "stcat_pl_conv_fwd": "pppppppppppp" + "iiiiiiiiii" + "s",
-    "stcat_pl_conv_dgrad": "ppppppppppppppp" + "iiiiiiiii" + "s",
-    "stcat_pl_linear_fwd": "ppppp" + "p" + "ppp" + "p" + "iiii" + "fllp" + "s",
-    "stcat_pl_linear_dgrad_mask": "pppp" + "pp" + "ppp" + "iii" + "s",
-    "stcat_pl_colsum": "pppiis",
-    "stcat_pl_split_sum": "ppppp" + "l" + "s",
-    "stcat_pl_conv_dgrad_cadd": "pppppp" + "i" + "pppp" + "iiiii" + "s",
-    "stcat_pl_conv_wgrad": "pppppp" + "iiiiiiiii" + "s",
-    "stcat_pl_conv_wgrad_ws": "pppppp" + "iiiiiiiii" + "pl" + "s",
-    "stcat_pl_maxpool3x3s2": "pppiiiis",
-    "stcat_pl_split": "pppls",
-    "stcat_pl_join": "pppls",
-    "stcat_pl_act_bwd": "ppppppp" + "lii" + "s",
-    "stcat_pl_scale": "ppppplis",
-    "stcat_weight_planes_entry_bytes": "",
-    "stcat_weight_planes_multi": "piis",
-    "stcat_debug_force_pl_tile": "i",
-    "stcat_debug_pl_flags": "i",
-    "stcat_debug_force_tile": "ii",
-    "stcat_debug_streamk": "i",
-    "stcat_spin": "is",
-    "stcat_stream_create": "iiP",
-    "stcat_stream_destroy": "P",
-    "stcat_set_mma_mode": "i",
-    "stcat_get_mma_mode": "",
-    "stcat_set_deterministic": "i",
-    "stcat_get_deterministic": "",
-    "stcat_set_f16_scales": "ii",
-    "stcat_get_f16_scale": "i",
-    # launch plans (csrc/launch_plan.h): P = host pointer, u = unsigned 64-bit, S = C string
-    "stcat_plan_fn_index": "S",
-    "stcat_plan_fn_nargs": "i",
-    "stcat_plan_create": "",
-    "stcat_plan_destroy": "P",
-    "stcat_plan_add_call": "PiPiii",
-    "stcat_plan_add_wait": "Pii",
-    "stcat_plan_add_memset": "Ppuii",
-    "stcat_plan_set_word": "Piu",
-    "stcat_plan_add_yield": "Pi",
-    "stcat_plan_add_reloc": "Piiu",
-    "stcat_plan_size": "PPPP",
-    "stcat_plan_run": "PPiPiiPP",
-}
+# name -> argument kinds of the library bound last, read from the library's own table (_bind; csrc/entry_points.h):
+# p = device pointer, P = host pointer, s = stream (void*), S = C string, i = int, l = long, f = float, u = unsigned 64-bit
+SIGNATURES: Dict[str, str] = {}
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "s": ctypes.c_void_p,
        "P": ctypes.c_void_p,  # P = HOST pointer (small by-value arrays, plan handles)
        "u": ctypes.c_ulonglong, "S": ctypes.c_char_p}
@@ -135,10 +35,16 @@ class StcatHipError(RuntimeError):
 
 
 def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
-    for name, sig in SIGNATURES.items():
+    global SIGNATURES
+    lib.stcat_entry_name.restype = lib.stcat_entry_kinds.restype = ctypes.c_char_p
+    table = {lib.stcat_entry_name(i).decode(): lib.stcat_entry_kinds(i).decode() for i in range(lib.stcat_entry_count())}
+    for name, sig in table.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export it
+        if not set(sig) <= set(_CT):
+            raise StcatHipError(f"{name}: unknown argument kind in {sig!r}")
         fn.argtypes = [_CT[c] for c in sig]
         fn.restype = ctypes.c_int
+    SIGNATURES = table
     lib.stcat_plan_create.restype = ctypes.c_void_p
     lib.stcat_version.restype = ctypes.c_int
     lib.stcat_last_error.restype = ctypes.c_char_p

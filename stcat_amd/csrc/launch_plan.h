@@ -27,7 +27,8 @@ typedef int (*ThunkFn)(const uint64_t*);
 
 struct FnEntry {
   const char* name;
-  ThunkFn call;
+  const char* kinds;  // one letter per argument (entry_points.h)
+  ThunkFn call;       // nullptr: not recordable
   int nargs;
 };
 
@@ -57,6 +58,58 @@ struct Thunk<int (*)(A...), f> {
   static constexpr int nargs = (int)sizeof...(A);
 };
 
+// The kind letters of entry_points.h against an entry point's own C type: kinds_match<decltype(&fn)>(kinds).  The
+// letters are what the hosts build their argument types from and what a recorder packs the argument words by, so a
+// letter that disagrees with the prototype must not compile.
+constexpr int kinds_len(const char* k) { return *k ? 1 + kinds_len(k + 1) : 0; }
+constexpr bool same_str(const char* a, const char* b) { return *a == *b && (!*a || same_str(a + 1, b + 1)); }
+
+template <class T>
+constexpr bool kind_is(char k, bool last) {
+  switch (k) {
+    case 'i': return std::is_same<T, int>::value;
+    case 'l': return std::is_same<T, long>::value;
+    case 'f': return std::is_same<T, float>::value;
+    case 'u': return std::is_same<T, unsigned long long>::value;
+    case 'S': return std::is_same<T, const char*>::value;
+    case 's': return std::is_same<T, void*>::value && last;
+    case 'p':
+    case 'P': return std::is_pointer<T>::value && !std::is_same<T, const char*>::value;
+    default: return false;
+  }
+}
+
+template <class F>
+struct KindsOf;
+template <class R, class... A>
+struct KindsOf<R (*)(A...)> {
+  template <size_t... I>
+  static constexpr bool args(const char* k, std::index_sequence<I...>) {
+    return (kind_is<A>(k[I], I + 1 == sizeof...(A)) && ...);
+  }
+  // every entry point returns int; `returns_handle` marks the one that returns a void* (stcat_plan_create)
+  static constexpr bool match(const char* k, bool returns_handle) {
+    return (returns_handle ? std::is_same<R, void*>::value : std::is_same<R, int>::value) &&
+           kinds_len(k) == (int)sizeof...(A) && args(k, std::index_sequence_for<A...>{});
+  }
+};
+template <class F>
+constexpr bool kinds_match(const char* kinds, bool returns_handle = false) {
+  return KindsOf<F>::match(kinds, returns_handle);
+}
+
+// recordable: a stream-ordered launch (the stream comes last) that takes no host pointer
+constexpr bool recordable(const char* k) {
+  bool host = false;
+  char last = 0;
+  for (; *k; ++k) { host = host || *k == 'P'; last = *k; }
+  return last == 's' && !host;
+}
+template <bool rec, class F, F f>
+constexpr ThunkFn thunk_if() {
+  if constexpr (rec) return &Thunk<F, f>::call;
+  else return nullptr;
+}
 enum OpKind : uint8_t { OP_CALL = 0, OP_WAIT = 1, OP_MEMSET = 2, OP_YIELD = 3 };
 
 struct Op {

@@ -718,7 +718,7 @@ static bool stem_pl_mode() { return g_stem_pl && (g_mma_mode_raw == 3 || g_mma_m
 
 extern "C" {
 
-int stcat_version(void) { return 100; }
+int stcat_version(void) { return 101; }
 int stcat_set_mma_mode(int mode) {
   if (mode != 0 && mode != 2 && mode != 3 && mode != 4 && mode != 5 && mode != 6)
     return fail("set_mma_mode: mode must be 0 (f32), 2 (bf16x3), 3 (bf16x6), 4 (bf16x3 on two bf16 planes), 5 (bf16x6 on three) "
@@ -1997,98 +1997,33 @@ int stcat_pl_rowscale(void* h, void* l, const float* w, long rows, int C, int pe
 
 }  // extern "C"
 
-// ---- launch plans (launch_plan.h): record once, replay with one host call -----------------------------------------
-#include "launch_plan.h"
+// ---- the entry-point table (entry_points.h); launch plans (launch_plan.h): record once, replay with one host call ---
+#include "entry_points.h"
 
 namespace {
-#define STCAT_PLAN_FN(name) \
-  { #name, &stcat_plan::Thunk<decltype(&name), &name>::call, stcat_plan::Thunk<decltype(&name), &name>::nargs }
-const stcat_plan::FnEntry g_plan_fns[] = {
-    STCAT_PLAN_FN(stcat_frozen_bn_fold),
-    STCAT_PLAN_FN(stcat_stem_fwd),
-    STCAT_PLAN_FN(stcat_stem_u8_fwd),
-    STCAT_PLAN_FN(stcat_maxpool3x3s2),
-    STCAT_PLAN_FN(stcat_conv_fwd),
-    STCAT_PLAN_FN(stcat_conv_dgrad),
-    STCAT_PLAN_FN(stcat_weight_transpose),
-    STCAT_PLAN_FN(stcat_weight_transpose_multi),
-    STCAT_PLAN_FN(stcat_conv_wgrad),
-    STCAT_PLAN_FN(stcat_act_bwd),
-    STCAT_PLAN_FN(stcat_pos_sine_2d),
-    STCAT_PLAN_FN(stcat_sine_embed_fwd),
-    STCAT_PLAN_FN(stcat_sine_embed_bwd),
-    STCAT_PLAN_FN(stcat_linear_fwd),
-    STCAT_PLAN_FN(stcat_linear_dgrad),
-    STCAT_PLAN_FN(stcat_linear_fwd_acc),
-    STCAT_PLAN_FN(stcat_linear_dgrad_acc),
-    STCAT_PLAN_FN(stcat_linear_fwd_drop),
-    STCAT_PLAN_FN(stcat_linear_fwd_multi),
-    STCAT_PLAN_FN(stcat_linear_dgrad_multi),
-    STCAT_PLAN_FN(stcat_linear_wgrad_multi),
-    STCAT_PLAN_FN(stcat_linear_dgrad_mask),
-    STCAT_PLAN_FN(stcat_linear_wgrad),
-    STCAT_PLAN_FN(stcat_small_linear_fwd),
-    STCAT_PLAN_FN(stcat_small_linear_bwd),
-    STCAT_PLAN_FN(stcat_colsum),
-    STCAT_PLAN_FN(stcat_layernorm_fwd),
-    STCAT_PLAN_FN(stcat_layernorm_bwd),
-    STCAT_PLAN_FN(stcat_ew),
-    STCAT_PLAN_FN(stcat_spin),
-    STCAT_PLAN_FN(stcat_ew2d),
-    STCAT_PLAN_FN(stcat_stg_loss_fwd),
-    STCAT_PLAN_FN(stcat_stg_loss_bwd),
-    STCAT_PLAN_FN(stcat_dropout),
-    STCAT_PLAN_FN(stcat_mha_self_fwd),
-    STCAT_PLAN_FN(stcat_mha_self_bwd),
-    STCAT_PLAN_FN(stcat_mha_self_fwd_lse),
-    STCAT_PLAN_FN(stcat_mha_self_bwd_lse),
-    STCAT_PLAN_FN(stcat_mha_bs_fwd),
-    STCAT_PLAN_FN(stcat_mha_bs_bwd),
-    STCAT_PLAN_FN(stcat_attn_weights_mean),
-    STCAT_PLAN_FN(stcat_attn_q1_fwd),
-    STCAT_PLAN_FN(stcat_attn_q1_bwd),
-    STCAT_PLAN_FN(stcat_map2d_pool),
-    STCAT_PLAN_FN(stcat_map2d_cells),
-    STCAT_PLAN_FN(stcat_map2d_cells_bwd),
-    STCAT_PLAN_FN(stcat_map2d_pool_bwd),
-    STCAT_PLAN_FN(stcat_rowscale),
-    STCAT_PLAN_FN(stcat_grad_sqnorm),
-    STCAT_PLAN_FN(stcat_grad_sqnorm_ws),
-    STCAT_PLAN_FN(stcat_grad_clip_scale),
-    STCAT_PLAN_FN(stcat_ema_update),
-    STCAT_PLAN_FN(stcat_temporal_map_argmax),
-    STCAT_PLAN_FN(stcat_pl_conv_fwd),
-    STCAT_PLAN_FN(stcat_pl_conv_dgrad),
-    STCAT_PLAN_FN(stcat_pl_conv_dgrad_cadd),
-    STCAT_PLAN_FN(stcat_pl_linear_fwd),
-    STCAT_PLAN_FN(stcat_pl_linear_dgrad_mask),
-    STCAT_PLAN_FN(stcat_pl_colsum),
-    STCAT_PLAN_FN(stcat_pl_split_sum),
-    STCAT_PLAN_FN(stcat_pl_conv_wgrad),
-    STCAT_PLAN_FN(stcat_pl_conv_wgrad_ws),
-    STCAT_PLAN_FN(stcat_pl_maxpool3x3s2),
-    STCAT_PLAN_FN(stcat_pl_split),
-    STCAT_PLAN_FN(stcat_pl_join),
-    STCAT_PLAN_FN(stcat_pl_act_bwd),
-    STCAT_PLAN_FN(stcat_pl_scale),
-    STCAT_PLAN_FN(stcat_weight_planes_multi),
-    STCAT_PLAN_FN(stcat_map2d_cells_bwd_gather),
-    STCAT_PLAN_FN(stcat_map2d_pool_bwd_gather),
-    STCAT_PLAN_FN(stcat_pl_rowscale),
-};
-constexpr int kPlanFns = (int)(sizeof(g_plan_fns) / sizeof(g_plan_fns[0]));
+// every entry point of the list; the recordable ones (stcat_plan::recordable) carry the thunk a replay calls them through
+#define STCAT_ENTRY(name, kinds)                                                                 \
+  {#name, kinds, stcat_plan::thunk_if<stcat_plan::recordable(kinds), decltype(&name), &name>(), \
+   stcat_plan::kinds_len(kinds)},
+const stcat_plan::FnEntry g_entries[] = {STCAT_ENTRY_POINTS(STCAT_ENTRY)};
+#undef STCAT_ENTRY
+constexpr int kEntries = (int)(sizeof(g_entries) / sizeof(g_entries[0]));
 inline stcat_plan::Plan* plan_of(void* h) { return static_cast<stcat_plan::Plan*>(h); }
 }  // namespace
 
 extern "C" {
 
+int stcat_entry_count(void) { return kEntries; }
+const char* stcat_entry_name(int i) { return (i >= 0 && i < kEntries) ? g_entries[i].name : nullptr; }
+const char* stcat_entry_kinds(int i) { return (i >= 0 && i < kEntries) ? g_entries[i].kinds : nullptr; }
+
 int stcat_plan_fn_index(const char* name) {
-  for (int i = 0; i < kPlanFns; ++i)
-    if (strcmp(g_plan_fns[i].name, name) == 0) return i;
+  for (int i = 0; i < kEntries; ++i)
+    if (g_entries[i].call && strcmp(g_entries[i].name, name) == 0) return i;
   return -1;
 }
 
-int stcat_plan_fn_nargs(int fn) { return (fn >= 0 && fn < kPlanFns) ? g_plan_fns[fn].nargs : -1; }
+int stcat_plan_fn_nargs(int fn) { return (fn >= 0 && fn < kEntries && g_entries[fn].call) ? g_entries[fn].nargs : -1; }
 
 void* stcat_plan_create(void) { return new stcat_plan::Plan(); }
 
@@ -2105,8 +2040,8 @@ int stcat_plan_destroy(void* h) {
 
 int stcat_plan_add_call(void* h, int fn, const unsigned long long* words, int nargs, int slot, int stream_arg) {
   stcat_plan::Plan* pl = plan_of(h);
-  if (!pl || fn < 0 || fn >= kPlanFns) return fail("plan_add_call: unknown entry point %d", fn);
-  if (nargs != g_plan_fns[fn].nargs) return fail("plan_add_call: %s takes %d arguments, got %d", g_plan_fns[fn].name, g_plan_fns[fn].nargs, nargs);
+  if (!pl || fn < 0 || fn >= kEntries || !g_entries[fn].call) return fail("plan_add_call: unknown entry point %d", fn);
+  if (nargs != g_entries[fn].nargs) return fail("plan_add_call: %s takes %d arguments, got %d", g_entries[fn].name, g_entries[fn].nargs, nargs);
   if (slot < 0 || slot > 250 || stream_arg >= nargs) return fail("plan_add_call: bad stream slot / position");
   stcat_plan::Op op = {};
   op.kind = stcat_plan::OP_CALL; op.slot = (uint8_t)slot; op.fn = fn; op.arg0 = (uint32_t)pl->words.size(); op.nargs = nargs;
@@ -2194,11 +2129,11 @@ int stcat_plan_run(void* h, const unsigned long long* ext, int n_ext, void* cons
     switch (op.kind) {
       case stcat_plan::OP_CALL: {
         if (op.stream_arg >= 0) w[op.arg0 + op.stream_arg] = (uint64_t)(uintptr_t)streams[op.slot];
-        const int rc = g_plan_fns[op.fn].call(w + op.arg0);
+        const int rc = g_entries[op.fn].call(w + op.arg0);
         if (rc != 0) {
           char inner[400];
           snprintf(inner, sizeof(inner), "%s", g_err);
-          snprintf(g_err, sizeof(g_err), "plan op %d (%s): %s", i, g_plan_fns[op.fn].name, inner);
+          snprintf(g_err, sizeof(g_err), "plan op %d (%s): %s", i, g_entries[op.fn].name, inner);
           return rc;
         }
         break;

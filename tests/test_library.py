@@ -13,16 +13,71 @@ from stcat_amd import _lib as L
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+SELF_DESCRIBING = {"stcat_version", "stcat_last_error", "stcat_entry_count", "stcat_entry_name", "stcat_entry_kinds"}
+
+
+def _entry_table(path):
+    """name -> kinds, read from a fresh handle of the library through its own three functions"""
+    lib = ctypes.CDLL(path)
+    lib.stcat_entry_name.restype = lib.stcat_entry_kinds.restype = ctypes.c_char_p
+    n = lib.stcat_entry_count()
+    assert lib.stcat_entry_name(-1) is None and lib.stcat_entry_kinds(-1) is None
+    assert lib.stcat_entry_name(n) is None and lib.stcat_entry_kinds(n) is None
+    table = {lib.stcat_entry_name(i).decode(): lib.stcat_entry_kinds(i).decode() for i in range(n)}
+    assert len(table) == n
+    return lib, table
+
+
+def _header_prototypes():
+    """name -> parameter count of every prototype in include/stcat_hip.h (comments stripped; `(void)` is 0)"""
+    header = open(os.path.join(ROOT, "include", "stcat_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    protos = {}
+    for name, params in re.findall(r"\b(stcat_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header):
+        assert name not in protos, name
+        protos[name] = 0 if params.strip() == "void" else len(params.split(","))
+    return protos
+
+
 def test_build_and_symbols():
     entry.build()
     header = open(os.path.join(ROOT, "include", "stcat_hip.h")).read()
     declared = set(re.findall(r"\b(stcat_[a-z0-9_]+)\s*\(", header))
     assert len(declared) >= 25
-    lib = ctypes.CDLL(entry.LIB)
+    lib, table = _entry_table(entry.LIB)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in stcat_hip.h but not exported"
-    bound = set(L.SIGNATURES) | {"stcat_version", "stcat_last_error"}
+    bound = set(table) | SELF_DESCRIBING
     assert declared == bound, declared ^ bound
+    protos = _header_prototypes()
+    assert set(protos) == declared, set(protos) ^ declared
+    for name, kinds in table.items():
+        assert len(kinds) == protos[name], (name, kinds, protos[name])
+    assert L._bind(ctypes.CDLL(entry.LIB)) and L.SIGNATURES == table
+
+
+def test_emulator_build_exports_the_same_table():
+    """product and emulator builds compile one list (csrc/entry_points.h): the tables agree name by name, in order"""
+    from tests import backends
+    entry.build()
+    backends._build_emu()
+    if backends._emu_state["error"]:
+        pytest.skip("host emulator build failed: " + backends._emu_state["error"])
+    _, emu = _entry_table(backends.EMU_SO)
+    _, hip = _entry_table(entry.LIB)
+    assert list(emu) == list(hip), set(emu) ^ set(hip)
+    for name in hip:
+        assert emu[name] == hip[name], (name, emu[name], hip[name])
+    assert set("".join(emu.values())) <= set(L._CT)
+
+
+def test_bind_refuses_an_unknown_kind_letter(monkeypatch):
+    entry.build()
+    monkeypatch.delitem(L._CT, "u")
+    saved = L.SIGNATURES
+    with pytest.raises(L.StcatHipError, match="unknown argument kind"):
+        L._bind(ctypes.CDLL(entry.LIB))
+    assert L.SIGNATURES is saved
 
 
 def test_invalid_arguments_report_errors():

@@ -192,6 +192,41 @@ def test_plan_table_covers_every_launch_entry_point():
             assert fn >= 0, name
             assert lib.stcat_plan_fn_nargs(fn) == len(sig), (name, lib.stcat_plan_fn_nargs(fn), len(sig))
     assert lib.stcat_plan_fn_index(b"stcat_set_mma_mode") == -1
+    assert "P" in _lib.SIGNATURES["stcat_adamw_ema_step"] and _lib.SIGNATURES["stcat_adamw_ema_step"].endswith("s")
+    assert lib.stcat_plan_fn_index(b"stcat_adamw_ema_step") == -1       # stream-ordered, but takes host pointers
+
+
+def test_emu_plan_words_keep_long_and_float_arguments():
+    """the argument words of a recorded call, packed by the kinds the library reports: stcat_dropout (ppplfllps) with a
+    seed above 2^32 and p = 0.5, replayed into a second buffer, draws the mask of the eager call and of the host twin of
+    the generator — an `l` read as an int would lose the seed's high half, an `f` read as an integer would lose p"""
+    import ctypes
+    dev = use_emu()
+    lib = _lib.load()
+    assert _lib.SIGNATURES["stcat_dropout"] == "ppplfllps"
+    n, p, seed, off = 4096, 0.5, (1 << 40) + 3, 1000
+    x = torch.arange(1, n + 1, dtype=torch.float32, device=dev)
+    eager, replayed = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    rec = plans.Recorder(dev, [replayed])
+    _lib.RECORDER = rec
+    try:
+        _lib.call("stcat_dropout", x.data_ptr(), None, eager.data_ptr(), n, p, seed, off, None, None)
+    finally:
+        _lib.RECORDER = None
+    try:
+        (w0, sig, words), = rec.calls
+        assert sig == "ppplfllps" and words[5] == seed
+        assert lib.stcat_plan_add_reloc(rec.h, w0 + 2, 0, 0) == 0
+        nxt, tag = ctypes.c_int(0), ctypes.c_int(0)
+        rc = lib.stcat_plan_run(rec.h, (ctypes.c_ulonglong * 1)(replayed.data_ptr()), 1, (ctypes.c_void_p * 1)(None), 1, 0,
+                                ctypes.byref(nxt), ctypes.byref(tag))
+        assert rc == 0 and nxt.value == -1, lib.stcat_last_error()
+    finally:
+        lib.stcat_plan_destroy(rec.h)
+    keep = torch.from_numpy(ops.dropout_keep_mask(seed, off, n, p))
+    assert 0.4 * n < int(keep.sum()) < 0.6 * n
+    assert torch.equal(eager, torch.where(keep, x / (1.0 - p), torch.zeros(())))
+    assert torch.equal(replayed, eager)
 
 
 class _NodeWithForeignKernel(torch.autograd.Function):
