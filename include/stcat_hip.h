@@ -272,7 +272,8 @@ int stcat_small_linear_bwd(const float* g, const float* x, const float* w, float
                            int N, int K, void* stream);
 /* out[N] (caller-zeroed) += sum_m a[m,n] * (b ? b[m,n] : 1) */
 int stcat_colsum(const float* a, const float* b, float* out, int M, int N, void* stream);
-/* LayerNorm over 256 features of (res + dropout_p(x)); saves mean / rstd per row.  The (drop_p, drop_seed,
+/* LayerNorm over D = 256 or D = 768 features of (res + dropout_p(x)); saves mean / rstd per row.  (At D = 768, the text
+ * encoder's width, dgamma / dbeta are summed by a single adder per column in either mode: no float atomic.)  The (drop_p, drop_seed,
  * drop_offset, drop_base) quadruple is the dropout of the residual branch (see "dropout" below; drop_p = 0: plain
  * x + res).  Backward: dz = gradient of res (and of x when drop_p = 0), dx (may be NULL when drop_p = 0) = mask * dz. */
 int stcat_layernorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* y,
@@ -293,8 +294,39 @@ int stcat_ew2d(int op, const float* a, long lda, const float* b, long ldb, float
 enum {
   STCAT_EW_ADD = 0, STCAT_EW_MUL = 1, STCAT_EW_SIGMOID = 2, STCAT_EW_TANH = 3, STCAT_EW_RELU = 4,
   STCAT_EW_INVSIG = 5, STCAT_EW_SIGMOID_BWD = 6, STCAT_EW_TANH_BWD = 7, STCAT_EW_INVSIG_BWD = 8,
-  STCAT_EW_ADD3 = 9, STCAT_EW_AXPBY = 10, STCAT_EW_COPY = 11
+  STCAT_EW_ADD3 = 9, STCAT_EW_AXPBY = 10, STCAT_EW_COPY = 11,
+  /* erf-GELU x / 2 (1 + erf(x / sqrt 2)) and its backward (a = dy, b = x): 16-byte accesses, any n, aligned pointers */
+  STCAT_EW_GELU = 12, STCAT_EW_GELU_BWD = 13
 };
+
+/* ---- text encoder (RoBERTa-base geometry) ------------------------------------------------------- */
+/* y[t] = dropout_p(LayerNorm(word[ids[t]] + pos[pos_ids[t]] + type[0])) over D = 768, one row per token; ids / pos_ids
+ * are int64 device vectors of L entries, V / P the row counts of the word / position tables.  The kernels never read a
+ * table row outside [0, V) / [0, P): such a token's output row is NaN (the host wrapper refuses the ids beforehand).
+ * Backward: de = [L,768] scratch; dword [V,768] and dpos [P,768] are caller-zeroed and receive their rows by a gather (the
+ * first position of an id sums every position that holds it, in ascending order); dtype / dgamma / dbeta [768] are
+ * caller-zeroed accumulators summed by a fixed tree.  Row `pad` of both tables (padding_idx; -1 = none) is never written.
+ * No float atomics. */
+int stcat_embed_ln_fwd(const long* ids, const long* pos_ids, const float* word, const float* pos, const float* type,
+                       const float* gamma, const float* beta, float* y, float* mean, float* rstd, int L, int D, int V,
+                       int P, float eps, float drop_p, long drop_seed, long drop_offset, const long* drop_base,
+                       void* stream);
+int stcat_embed_ln_bwd(const float* dy, const long* ids, const long* pos_ids, const float* word, const float* pos,
+                       const float* type, const float* gamma, const float* mean, const float* rstd, float* de,
+                       float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta, int L, int D, int V, int P,
+                       int pad, float drop_p, long drop_seed, long drop_offset, const long* drop_base, void* stream);
+/* softmax(scale * q k^T + key_padding) v per (batch, head) with head dimension 64, 1 <= S <= 128 (longer rows: -1, the
+ * error text names the limit); q/k/v/o are [B,S,ld*] with head h at column 64 h; kpm [B,S] bytes (non-zero = padded key)
+ * or NULL.  fp32 arithmetic in every mma mode.  p (may be NULL: inference) receives the probabilities [B,H,S,S] before
+ * dropout; dropout decision of (query, key): counter ((b H + h) Sp + key) Sp + query, Sp = 32 ceil(S / 32).
+ * Backward: delta = [B,H,S] scratch; dq / dk are [B,S,ldg], dv is [B,S,ldgv]; every row has one writer. */
+int stcat_mha_d64_fwd(const float* q, const float* k, const float* v, const unsigned char* kpm, float* o, float* p, int B,
+                      int H, int S, int ldq, int ldk, int ldv, int ldo, float scale, float drop_p, long drop_seed,
+                      long drop_offset, const long* drop_base, void* stream);
+int stcat_mha_d64_bwd(const float* q, const float* k, const float* v, const float* dout, const float* p, float* delta,
+                      float* dq, float* dk, float* dv, int B, int H, int S, int ldq, int ldk, int ldv, int ldo, int ldg,
+                      int ldgv, float scale, float drop_p, long drop_seed, long drop_offset, const long* drop_base,
+                      void* stream);
 
 /* ---- dropout (train mode) ----------------------------------------------------------------------- */
 /* y = res + dropout_p(x)  (res may be NULL): nn.Dropout at modal_encoder.py:237-240, query_decoder.py:344,

@@ -6,7 +6,7 @@ Two ways in:
 
       import stcat_amd; stcat_amd.install()      # before models.build_model(cfg)
 
-  rebinds the three factory names that ``models/pipeline.py:6-8`` imports
+  rebinds the three factory names (four with ``install(text_encoder=True)``) that ``models/pipeline.py:6-8`` imports
   (``build_vis_encoder``, ``build_encoder``, ``build_decoder``) so ``STCATNet`` is built from the
   HIP-backed modules; every reference file stays byte-identical.
 
@@ -31,9 +31,11 @@ def is_deterministic() -> bool:
     return _lib.is_deterministic()
 
 
-def install():
+def install(text_encoder: bool = False):
     """Rebind the reference's factory seam.  Requires the reference package ``models``
-    to be importable; must run before ``STCATNet`` is constructed."""
+    to be importable; must run before ``STCATNet`` is constructed.  ``text_encoder=True`` also rebinds
+    ``build_text_encoder`` (the native RoBERTa node, stcat_amd.text; pass it a tokenizer with
+    ``functools.partial(build_text_encoder, tokenizer=...)`` or set ``model.text_encoder.tokenizer``)."""
     import importlib
 
     from .backbone import build_vis_encoder
@@ -48,4 +50,9 @@ def install():
     vision.build_vis_encoder = build_vis_encoder
     grounding.build_encoder = build_encoder
     grounding.build_decoder = build_decoder
+    if text_encoder:
+        from .text import build_text_encoder
+        language = importlib.import_module("models.language_model")
+        pipeline.build_text_encoder = build_text_encoder
+        language.build_text_encoder = build_text_encoder
     return pipeline

@@ -25,6 +25,7 @@ _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.
 
 EW_ADD, EW_MUL, EW_SIGMOID, EW_TANH, EW_RELU, EW_INVSIG = 0, 1, 2, 3, 4, 5
 EW_SIGMOID_BWD, EW_TANH_BWD, EW_INVSIG_BWD, EW_ADD3, EW_AXPBY, EW_COPY = 6, 7, 8, 9, 10, 11
+EW_GELU, EW_GELU_BWD = 12, 13       # erf-GELU and its backward (a = dy, b = x)
 
 _lib: Optional[ctypes.CDLL] = None
 _backend = "hip"

@@ -45,6 +45,10 @@
   X(stcat_layernorm_bwd, "ppppppppppiifllps") \
   X(stcat_ew, "ippppllffs") \
   X(stcat_ew2d, "iplplplliffs") \
+  X(stcat_embed_ln_fwd, "ppppppppppiiiiffllps") \
+  X(stcat_embed_ln_bwd, "pppppppppppppppiiiiifllps") \
+  X(stcat_mha_d64_fwd, "ppppppiiiiiiiffllps") \
+  X(stcat_mha_d64_bwd, "pppppppppiiiiiiiiiffllps") \
   X(stcat_stg_loss_fwd, "pppppppppppppfiiiiippps") \
   X(stcat_stg_loss_bwd, "pppppppppppppfiiiiippppppps") \
   X(stcat_dropout, "ppplfllps") \

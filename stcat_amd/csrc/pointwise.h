@@ -8,33 +8,57 @@
 
 // ---------------------------------------------------------------------------------
 // LayerNorm over D = 256 (torch.nn.LayerNorm(256), eps 1e-5: modal_encoder.py:218-219,
-// query_decoder.py:296-299, 573-576).  One wave per row, one float4 per lane.
+// query_decoder.py:296-299, 573-576) or D = 768 (the text encoder).  One wave per row, D / 256 float4 per lane.
 // ---------------------------------------------------------------------------------
 // y = LayerNorm(res + dropout(x)): the dropout of the residual branch (modal_encoder.py:237-240 and friends) is
-// applied in-register from its counter-based mask; drop.thresh == 0 means no dropout
+// applied in-register from its counter-based mask; drop.thresh == 0 means no dropout.
+// DV = D / 256 float4 per lane: 1 (the grounding model's 256 features) or 3 (the text encoder's 768); lane l holds columns
+// j * 256 + 4 l .. + 3 of block j, so DV = 1 is the kernel it always was (same grid, same order of every sum).
+template <int DV>
 __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* x, const float* res, const float* gamma,
                                                            const float* beta, float* y, float* mean, float* rstd,
                                                            int M, float eps, DropParams drop) {
+  constexpr int D = 256 * DV;
   drop = stcat_drop_resolve(drop);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const float4 g = stcat_ld4(gamma + lane * 4), bt = stcat_ld4(beta + lane * 4);
+  float4 g[DV], bt[DV];
+  STCAT_UNROLL
+  for (int j = 0; j < DV; ++j) {
+    g[j] = stcat_ld4(gamma + j * 256 + lane * 4);
+    bt[j] = stcat_ld4(beta + j * 256 + lane * 4);
+  }
   for (int row = blockIdx.x * 4 + w; row < M; row += gridDim.x * 4) {
-    float4 v = stcat_ld4(x + (long)row * 256 + lane * 4);
-    if (drop.thresh) {
-      const unsigned long long c0 = (unsigned long long)row * 256 + lane * 4;
-      v.x *= stcat_drop_mul(drop, c0); v.y *= stcat_drop_mul(drop, c0 + 1);
-      v.z *= stcat_drop_mul(drop, c0 + 2); v.w *= stcat_drop_mul(drop, c0 + 3);
+    float4 v[DV];
+    STCAT_UNROLL
+    for (int j = 0; j < DV; ++j) {
+      const int c = j * 256 + lane * 4;
+      v[j] = stcat_ld4(x + (long)row * D + c);
+      if (drop.thresh) {
+        const unsigned long long c0 = (unsigned long long)row * D + c;
+        v[j].x *= stcat_drop_mul(drop, c0); v[j].y *= stcat_drop_mul(drop, c0 + 1);
+        v[j].z *= stcat_drop_mul(drop, c0 + 2); v[j].w *= stcat_drop_mul(drop, c0 + 3);
+      }
+      if (res) {
+        const float4 r = stcat_ld4(res + (long)row * D + c);
+        v[j].x += r.x; v[j].y += r.y; v[j].z += r.z; v[j].w += r.w;
+      }
     }
-    if (res) {
-      const float4 r = stcat_ld4(res + (long)row * 256 + lane * 4);
-      v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-    }
-    const float mu = stcat_wave_sum(v.x + v.y + v.z + v.w) * (1.f / 256.f);
-    const float dx = v.x - mu, dy = v.y - mu, dz = v.z - mu, dw = v.w - mu;
-    const float var = stcat_wave_sum(dx * dx + dy * dy + dz * dz + dw * dw) * (1.f / 256.f);
+    float s = v[0].x + v[0].y + v[0].z + v[0].w;
+    STCAT_UNROLL
+    for (int j = 1; j < DV; ++j) s += v[j].x + v[j].y + v[j].z + v[j].w;
+    const float mu = stcat_wave_sum(s) * (1.f / D);
+    STCAT_UNROLL
+    for (int j = 0; j < DV; ++j) { v[j].x -= mu; v[j].y -= mu; v[j].z -= mu; v[j].w -= mu; }
+    float q = v[0].x * v[0].x + v[0].y * v[0].y + v[0].z * v[0].z + v[0].w * v[0].w;
+    STCAT_UNROLL
+    for (int j = 1; j < DV; ++j) q += v[j].x * v[j].x + v[j].y * v[j].y + v[j].z * v[j].z + v[j].w * v[j].w;
+    const float var = stcat_wave_sum(q) * (1.f / D);
     const float rs = 1.f / sqrtf(var + eps);
-    stcat_st4(y + (long)row * 256 + lane * 4,
-              make_float4(dx * rs * g.x + bt.x, dy * rs * g.y + bt.y, dz * rs * g.z + bt.z, dw * rs * g.w + bt.w));
+    STCAT_UNROLL
+    for (int j = 0; j < DV; ++j)
+      stcat_st4(y + (long)row * D + j * 256 + lane * 4,
+                make_float4(v[j].x * rs * g[j].x + bt[j].x, v[j].y * rs * g[j].y + bt[j].y,
+                            v[j].z * rs * g[j].z + bt[j].z, v[j].w * rs * g[j].w + bt[j].w));
     if (lane == 0) {
       mean[row] = mu;
       rstd[row] = rs;
@@ -44,50 +68,77 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const float* x, cons
 
 // dz = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma; dgamma += dy * xhat, dbeta += dy
 // with dropout: dz is the gradient of the residual input, dx = mask * dz the gradient of the dropped branch
+template <int DV>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const float* dy, const float* x, const float* res,
                                                            const float* gamma, const float* mean, const float* rstd,
                                                            float* dz, float* dx, float* dgamma, float* dbeta, int M,
                                                            DropParams drop) {
+  constexpr int D = 256 * DV;
   drop = stcat_drop_resolve(drop);
-  __shared__ float red[2][4][256];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const float4 g = stcat_ld4(gamma + lane * 4);
-  float4 ag = make_float4(0.f, 0.f, 0.f, 0.f), ab = ag;
-  for (int row = blockIdx.x * 4 + w; row < M; row += gridDim.x * 4) {
-    float4 v = stcat_ld4(x + (long)row * 256 + lane * 4);
-    float4 dm = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (drop.thresh) {
-      const unsigned long long c0 = (unsigned long long)row * 256 + lane * 4;
-      dm = make_float4(stcat_drop_mul(drop, c0), stcat_drop_mul(drop, c0 + 1), stcat_drop_mul(drop, c0 + 2),
-                       stcat_drop_mul(drop, c0 + 3));
-      v.x *= dm.x; v.y *= dm.y; v.z *= dm.z; v.w *= dm.w;
-    }
-    if (res) {
-      const float4 r = stcat_ld4(res + (long)row * 256 + lane * 4);
-      v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-    }
-    const float4 d = stcat_ld4(dy + (long)row * 256 + lane * 4);
-    const float mu = mean[row], rs = rstd[row];
-    const float hx = (v.x - mu) * rs, hy = (v.y - mu) * rs, hz = (v.z - mu) * rs, hw = (v.w - mu) * rs;
-    const float gx = d.x * g.x, gy = d.y * g.y, gz = d.z * g.z, gw = d.w * g.w;
-    const float c1 = stcat_wave_sum(gx + gy + gz + gw) * (1.f / 256.f);
-    const float c2 = stcat_wave_sum(gx * hx + gy * hy + gz * hz + gw * hw) * (1.f / 256.f);
-    const float4 dzv = make_float4(rs * (gx - c1 - hx * c2), rs * (gy - c1 - hy * c2), rs * (gz - c1 - hz * c2),
-                                   rs * (gw - c1 - hw * c2));
-    stcat_st4(dz + (long)row * 256 + lane * 4, dzv);
-    if (dx) stcat_st4(dx + (long)row * 256 + lane * 4, make_float4(dzv.x * dm.x, dzv.y * dm.y, dzv.z * dm.z, dzv.w * dm.w));
-    ag.x += d.x * hx; ag.y += d.y * hy; ag.z += d.z * hz; ag.w += d.w * hw;
-    ab.x += d.x; ab.y += d.y; ab.z += d.z; ab.w += d.w;
+  float4 g[DV], ag[DV], ab[DV];
+  STCAT_UNROLL
+  for (int j = 0; j < DV; ++j) {
+    g[j] = stcat_ld4(gamma + j * 256 + lane * 4);
+    ag[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    ab[j] = ag[j];
   }
-  float* r0 = &red[0][w][lane * 4];
-  float* r1 = &red[1][w][lane * 4];
-  r0[0] = ag.x; r0[1] = ag.y; r0[2] = ag.z; r0[3] = ag.w;
-  r1[0] = ab.x; r1[1] = ab.y; r1[2] = ab.z; r1[3] = ab.w;
-  __syncthreads();
-  const int c = threadIdx.x;
-  if (!dgamma) return;  // deterministic mode: layernorm_bwd_affine_det_kernel owns dgamma / dbeta
-  atomicAdd(dgamma + c, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
-  atomicAdd(dbeta + c, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+  for (int row = blockIdx.x * 4 + w; row < M; row += gridDim.x * 4) {
+    const float mu = mean[row], rs = rstd[row];
+    float4 h[DV], gg[DV], dm[DV], d[DV];
+    STCAT_UNROLL
+    for (int j = 0; j < DV; ++j) {
+      const int c = j * 256 + lane * 4;
+      float4 v = stcat_ld4(x + (long)row * D + c);
+      dm[j] = make_float4(1.f, 1.f, 1.f, 1.f);
+      if (drop.thresh) {
+        const unsigned long long c0 = (unsigned long long)row * D + c;
+        dm[j] = make_float4(stcat_drop_mul(drop, c0), stcat_drop_mul(drop, c0 + 1), stcat_drop_mul(drop, c0 + 2),
+                            stcat_drop_mul(drop, c0 + 3));
+        v.x *= dm[j].x; v.y *= dm[j].y; v.z *= dm[j].z; v.w *= dm[j].w;
+      }
+      if (res) {
+        const float4 r = stcat_ld4(res + (long)row * D + c);
+        v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+      }
+      d[j] = stcat_ld4(dy + (long)row * D + c);
+      h[j] = make_float4((v.x - mu) * rs, (v.y - mu) * rs, (v.z - mu) * rs, (v.w - mu) * rs);
+      gg[j] = make_float4(d[j].x * g[j].x, d[j].y * g[j].y, d[j].z * g[j].z, d[j].w * g[j].w);
+    }
+    float s1 = gg[0].x + gg[0].y + gg[0].z + gg[0].w;
+    float s2 = gg[0].x * h[0].x + gg[0].y * h[0].y + gg[0].z * h[0].z + gg[0].w * h[0].w;
+    STCAT_UNROLL
+    for (int j = 1; j < DV; ++j) {
+      s1 += gg[j].x + gg[j].y + gg[j].z + gg[j].w;
+      s2 += gg[j].x * h[j].x + gg[j].y * h[j].y + gg[j].z * h[j].z + gg[j].w * h[j].w;
+    }
+    const float c1 = stcat_wave_sum(s1) * (1.f / D);
+    const float c2 = stcat_wave_sum(s2) * (1.f / D);
+    STCAT_UNROLL
+    for (int j = 0; j < DV; ++j) {
+      const int c = j * 256 + lane * 4;
+      const float4 dzv = make_float4(rs * (gg[j].x - c1 - h[j].x * c2), rs * (gg[j].y - c1 - h[j].y * c2),
+                                     rs * (gg[j].z - c1 - h[j].z * c2), rs * (gg[j].w - c1 - h[j].w * c2));
+      stcat_st4(dz + (long)row * D + c, dzv);
+      if (dx) stcat_st4(dx + (long)row * D + c, make_float4(dzv.x * dm[j].x, dzv.y * dm[j].y, dzv.z * dm[j].z, dzv.w * dm[j].w));
+      ag[j].x += d[j].x * h[j].x; ag[j].y += d[j].y * h[j].y; ag[j].z += d[j].z * h[j].z; ag[j].w += d[j].w * h[j].w;
+      ab[j].x += d[j].x; ab[j].y += d[j].y; ab[j].z += d[j].z; ab[j].w += d[j].w;
+    }
+  }
+  // The atomic epilogue exists at D = 256 only (default mode); at D = 768 the affine gradients always belong to
+  // layernorm_bwd_affine_det_kernel, so that instantiation holds no atomic and no LDS.
+  if constexpr (DV == 1) {
+    __shared__ float red[2][4][256];
+    if (!dgamma) return;  // deterministic mode: layernorm_bwd_affine_det_kernel owns dgamma / dbeta
+    float* r0 = &red[0][w][lane * 4];
+    float* r1 = &red[1][w][lane * 4];
+    r0[0] = ag[0].x; r0[1] = ag[0].y; r0[2] = ag[0].z; r0[3] = ag[0].w;
+    r1[0] = ab[0].x; r1[1] = ab[0].y; r1[2] = ab[0].z; r1[3] = ab[0].w;
+    __syncthreads();
+    const int c = threadIdx.x;
+    atomicAdd(dgamma + c, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
+    atomicAdd(dbeta + c, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+  }
 }
 
 // ---------------------------------------------------------------------------------
@@ -109,7 +160,8 @@ static __device__ __forceinline__ float stcat_det_lane_tree(float v, float (*red
   return red[0][cl];
 }
 
-// dgamma[c] += sum_m dy * xhat, dbeta[c] += sum_m dy with xhat recomputed as layernorm_bwd_kernel does (D = 256)
+// dgamma[c] += sum_m dy * xhat, dbeta[c] += sum_m dy with xhat recomputed as layernorm_bwd_kernel does (D = 256 DV; grid D / 32)
+template <int DV>
 __global__ void __launch_bounds__(STCAT_DET_COLS * STCAT_DET_LANES)
     layernorm_bwd_affine_det_kernel(const float* dy, const float* x, const float* res, const float* mean, const float* rstd,
                                     float* dgamma, float* dbeta, int M, DropParams drop) {
@@ -118,7 +170,7 @@ __global__ void __launch_bounds__(STCAT_DET_COLS * STCAT_DET_LANES)
   const int cl = threadIdx.x % STCAT_DET_COLS, rl = threadIdx.x / STCAT_DET_COLS, c = blockIdx.x * STCAT_DET_COLS + cl;
   float ag = 0.f, ab = 0.f;
   for (int row = rl; row < M; row += STCAT_DET_LANES) {
-    const long i = (long)row * 256 + c;
+    const long i = (long)row * (256 * DV) + c;
     float v = x[i];
     if (drop.thresh) v *= stcat_drop_mul(drop, (unsigned long long)i);
     if (res) v += res[i];
@@ -203,7 +255,8 @@ __global__ void __launch_bounds__(256) act_bwd_kernel(const float* dy, const flo
 // element-wise glue.  b is indexed modulo bmod (row broadcast when bmod == D).
 // ---------------------------------------------------------------------------------
 enum { EW_ADD = 0, EW_MUL = 1, EW_SIGMOID = 2, EW_TANH = 3, EW_RELU = 4, EW_INVSIG = 5, EW_SIGMOID_BWD = 6,
-       EW_TANH_BWD = 7, EW_INVSIG_BWD = 8, EW_ADD3 = 9, EW_AXPBY = 10, EW_COPY = 11 };
+       EW_TANH_BWD = 7, EW_INVSIG_BWD = 8, EW_ADD3 = 9, EW_AXPBY = 10, EW_COPY = 11,
+       EW_GELU = 12, EW_GELU_BWD = 13 /* both run in gelu_kernel (text_encoder.h) */ };
 
 __global__ void __launch_bounds__(256) ew_kernel(int op, const float* a, const float* b, const float* c, float* out,
                                                 long n, long bmod, float alpha, float beta) {

@@ -17,6 +17,7 @@
 #include "stem_pl.h"
 #include "pointwise.h"
 #include "loss.h"
+#include "text_encoder.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -1248,39 +1249,156 @@ int stcat_colsum(const float* a, const float* b, float* out, int M, int N, void*
 int stcat_layernorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                         float* mean, float* rstd, int M, int D, float eps, float drop_p, long drop_seed,
                         long drop_offset, const long* drop_base, void* stream) {
-  if (D != 256) return fail("layernorm: D must be 256 (got %d)", D);
-  STCAT_LAUNCH(layernorm_fwd_kernel, dim3(grid_for(M, 4, 2048)), dim3(256), 0, (hipStream_t)stream, x, res, gamma,
-               beta, y, mean, rstd, M, eps, stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
+  if (D != 256 && D != 768) return fail("layernorm: D must be 256 or 768 (got %d)", D);
+  const DropParams drop = stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base);
+  if (D == 768)
+    STCAT_LAUNCH(layernorm_fwd_kernel<3>, dim3(grid_for(M, 4, 2048)), dim3(256), 0, (hipStream_t)stream, x, res, gamma,
+                 beta, y, mean, rstd, M, eps, drop);
+  else
+    STCAT_LAUNCH(layernorm_fwd_kernel<1>, dim3(grid_for(M, 4, 2048)), dim3(256), 0, (hipStream_t)stream, x, res, gamma,
+                 beta, y, mean, rstd, M, eps, drop);
   return launch_status();
 }
 
 int stcat_layernorm_bwd(const float* dy, const float* x, const float* res, const float* gamma, const float* mean,
                         const float* rstd, float* dz, float* dx, float* dgamma, float* dbeta, int M, int D,
                         float drop_p, long drop_seed, long drop_offset, const long* drop_base, void* stream) {
-  if (D != 256) return fail("layernorm: D must be 256 (got %d)", D);
+  if (D != 256 && D != 768) return fail("layernorm: D must be 256 or 768 (got %d)", D);
   if (drop_p > 0.f && !dx) return fail("layernorm_bwd: dropout needs the dx output");
+  const DropParams drop = stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base);
+  if (D == 768) {
+    // the text encoder's width: dz / dx by the row kernel, the affine gradients ALWAYS by the single-adder column kernel
+    // (no float atomic in either mode)
+    STCAT_LAUNCH(layernorm_bwd_kernel<3>, dim3(grid_for(M, 4, 512)), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma,
+                 mean, rstd, dz, dx, (float*)nullptr, (float*)nullptr, M, drop);
+    if (int rc = launch_status()) return rc;
+    STCAT_LAUNCH(layernorm_bwd_affine_det_kernel<3>, dim3(768 / STCAT_DET_COLS), dim3(STCAT_DET_COLS * STCAT_DET_LANES), 0,
+                 (hipStream_t)stream, dy, x, res, mean, rstd, dgamma, dbeta, M, drop);
+    return launch_status();
+  }
   // small M (the decoders' [T,256] states): one row per wave, so the rows of a launch are normalised in parallel
   if (g_deterministic) {
     // dz / dx as always, the affine gradients by the single-adder column kernel (form "no split", pointwise.h)
-    STCAT_LAUNCH(layernorm_bwd_kernel, dim3(grid_for(M, M <= 1024 ? 4 : 16, 512)), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma,
-                 mean, rstd, dz, dx, (float*)nullptr, (float*)nullptr, M, stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
+    STCAT_LAUNCH(layernorm_bwd_kernel<1>, dim3(grid_for(M, M <= 1024 ? 4 : 16, 512)), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma,
+                 mean, rstd, dz, dx, (float*)nullptr, (float*)nullptr, M, drop);
     if (int rc = launch_status()) return rc;
-    STCAT_LAUNCH(layernorm_bwd_affine_det_kernel, dim3(256 / STCAT_DET_COLS), dim3(STCAT_DET_COLS * STCAT_DET_LANES), 0,
-                 (hipStream_t)stream, dy, x, res, mean, rstd, dgamma, dbeta, M,
-                 stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
+    STCAT_LAUNCH(layernorm_bwd_affine_det_kernel<1>, dim3(256 / STCAT_DET_COLS), dim3(STCAT_DET_COLS * STCAT_DET_LANES), 0,
+                 (hipStream_t)stream, dy, x, res, mean, rstd, dgamma, dbeta, M, drop);
     return launch_status();
   }
-  STCAT_LAUNCH(layernorm_bwd_kernel, dim3(grid_for(M, M <= 1024 ? 4 : 16, 512)), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma,
-               mean, rstd, dz, dx, dgamma, dbeta, M, stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
+  STCAT_LAUNCH(layernorm_bwd_kernel<1>, dim3(grid_for(M, M <= 1024 ? 4 : 16, 512)), dim3(256), 0, (hipStream_t)stream, dy, x, res, gamma,
+               mean, rstd, dz, dx, dgamma, dbeta, M, drop);
   return launch_status();
 }
 
 int stcat_ew(int op, const float* a, const float* b, const float* c, float* out, long n, long bmod, float alpha,
              float beta, void* stream) {
   if (n <= 0) return fail("ew: n=%ld", n);
+  if (op == EW_GELU || op == EW_GELU_BWD) {
+    if (op == EW_GELU_BWD && !b) return fail("ew: GELU backward takes dy (a) and x (b)");
+    if (!aligned16(a) || !aligned16(out) || (b && !aligned16(b))) return fail("ew: GELU operands must be 16-byte aligned");
+    STCAT_LAUNCH(gelu_kernel, dim3(grid_for((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                 op == EW_GELU_BWD ? 1 : 0, a, b, out, n);
+    return launch_status();
+  }
   if (bmod <= 0) bmod = n;
   STCAT_LAUNCH(ew_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, op, a, b, c, out, n, bmod,
                alpha, beta);
+  return launch_status();
+}
+
+// ---- text encoder (text_encoder.h) ---------------------------------------------------------------------------------
+int stcat_embed_ln_fwd(const long* ids, const long* pos_ids, const float* word, const float* pos, const float* type,
+                       const float* gamma, const float* beta, float* y, float* mean, float* rstd, int L, int D, int V,
+                       int P, float eps, float drop_p, long drop_seed, long drop_offset, const long* drop_base,
+                       void* stream) {
+  if (D != STCAT_TXT_D) return fail("embed_ln: D must be %d (got %d)", STCAT_TXT_D, D);
+  if (L <= 0 || V <= 0 || P <= 0) return fail("embed_ln: L=%d V=%d P=%d", L, V, P);
+  if (!ids || !pos_ids || !word || !pos || !type || !gamma || !beta || !y || !mean || !rstd) return fail("embed_ln_fwd: NULL operand");
+  if (!aligned16(word) || !aligned16(pos) || !aligned16(type) || !aligned16(gamma) || !aligned16(beta) || !aligned16(y))
+    return fail("embed_ln_fwd: tables, affine vectors and y must be 16-byte aligned");
+  STCAT_LAUNCH(embed_ln_fwd_kernel, dim3(cdiv(L, 4)), dim3(256), 0, (hipStream_t)stream, ids, pos_ids, word, pos, type,
+               gamma, beta, y, mean, rstd, L, V, P, eps, stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base));
+  return launch_status();
+}
+
+int stcat_embed_ln_bwd(const float* dy, const long* ids, const long* pos_ids, const float* word, const float* pos,
+                       const float* type, const float* gamma, const float* mean, const float* rstd, float* de,
+                       float* dword, float* dpos, float* dtype, float* dgamma, float* dbeta, int L, int D, int V, int P,
+                       int pad, float drop_p, long drop_seed, long drop_offset, const long* drop_base, void* stream) {
+  if (D != STCAT_TXT_D) return fail("embed_ln: D must be %d (got %d)", STCAT_TXT_D, D);
+  if (L <= 0 || V <= 0 || P <= 0) return fail("embed_ln: L=%d V=%d P=%d", L, V, P);
+  if (!dy || !ids || !pos_ids || !word || !pos || !type || !gamma || !mean || !rstd || !de || !dword || !dpos || !dtype ||
+      !dgamma || !dbeta)
+    return fail("embed_ln_bwd: NULL operand");
+  if (!aligned16(word) || !aligned16(pos) || !aligned16(type) || !aligned16(gamma) || !aligned16(dy) || !aligned16(de))
+    return fail("embed_ln_bwd: tables, gamma, dy and de must be 16-byte aligned");
+  const DropParams drop = stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base);
+  STCAT_LAUNCH(embed_ln_bwd_rows_kernel, dim3(cdiv(L, 4)), dim3(256), 0, (hipStream_t)stream, dy, ids, pos_ids, word, pos,
+               type, gamma, mean, rstd, de, L, V, P, drop);
+  if (int rc = launch_status()) return rc;
+  STCAT_LAUNCH(embed_ln_bwd_tables_kernel, dim3(L), dim3(256), 0, (hipStream_t)stream, (const float*)de, ids, pos_ids, dword,
+               dpos, L, V, P, pad);
+  if (int rc = launch_status()) return rc;
+  STCAT_LAUNCH(embed_ln_bwd_cols_kernel, dim3(STCAT_TXT_D / STCAT_DET_COLS), dim3(STCAT_DET_COLS * STCAT_DET_LANES), 0,
+               (hipStream_t)stream, dy, (const float*)de, ids, pos_ids, word, pos, type, mean, rstd, dtype, dgamma, dbeta, L,
+               V, P, drop);
+  return launch_status();
+}
+
+#define STCAT_MHA_D64_MAX_S 128
+// more than 64 KB of dynamic LDS is an opt-in per kernel (once)
+#ifdef STCAT_EMU
+#define STCAT_D64_PREPARE(kernel) ((void)0)
+#else
+#define STCAT_D64_PREPARE(kernel)                                                                                      \
+  do {                                                                                                                 \
+    static bool done_ = false;                                                                                         \
+    if (!done_) {                                                                                                      \
+      if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) != hipSuccess) \
+        return fail("mha_d64: cannot reserve 112 KB of LDS");                                                          \
+      done_ = true;                                                                                                    \
+    }                                                                                                                  \
+  } while (0)
+#endif
+
+int stcat_mha_d64_fwd(const float* q, const float* k, const float* v, const unsigned char* kpm, float* o, float* p, int B,
+                      int H, int S, int ldq, int ldk, int ldv, int ldo, float scale, float drop_p, long drop_seed,
+                      long drop_offset, const long* drop_base, void* stream) {
+  if (S > STCAT_MHA_D64_MAX_S) return fail("mha_d64_fwd: S=%d exceeds the limit of %d tokens", S, STCAT_MHA_D64_MAX_S);
+  if (S <= 0 || B <= 0 || H <= 0 || (long)B * H > 65535l * 1024) return fail("mha_d64_fwd: bad shape B=%d H=%d S=%d", B, H, S);
+  if (!q || !k || !v || !o) return fail("mha_d64_fwd: NULL operand");
+  if ((ldq | ldk | ldv) % 4 != 0 || ldq < 64 * H || ldk < 64 * H || ldv < 64 * H || ldo < 64 * H || !aligned16(q) ||
+      !aligned16(k) || !aligned16(v))
+    return fail("mha_d64_fwd: q/k/v must be 16-byte aligned with ld %% 4 == 0 and ld >= 64 H");
+  MhaD64Params a = {};
+  a.Q = q; a.K = k; a.V = v; a.kpm = kpm; a.O = o; a.Pout = p; a.B = B; a.H = H; a.S = S;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
+  a.drop = stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base);
+  STCAT_D64_PREPARE(mha_d64_fwd_kernel);
+  STCAT_LAUNCH(mha_d64_fwd_kernel, dim3(B * H, cdiv(S, 32)), dim3(256), mha_d64_fwd_lds(S), (hipStream_t)stream, a);
+  return launch_status();
+}
+
+int stcat_mha_d64_bwd(const float* q, const float* k, const float* v, const float* dout, const float* p, float* delta,
+                      float* dq, float* dk, float* dv, int B, int H, int S, int ldq, int ldk, int ldv, int ldo, int ldg,
+                      int ldgv, float scale, float drop_p, long drop_seed, long drop_offset, const long* drop_base,
+                      void* stream) {
+  if (S > STCAT_MHA_D64_MAX_S) return fail("mha_d64_bwd: S=%d exceeds the limit of %d tokens", S, STCAT_MHA_D64_MAX_S);
+  if (S <= 0 || B <= 0 || H <= 0 || (long)B * H > 65535l * 1024) return fail("mha_d64_bwd: bad shape B=%d H=%d S=%d", B, H, S);
+  if (!q || !k || !v || !dout || !p || !delta || !dq || !dk || !dv) return fail("mha_d64_bwd: NULL operand");
+  if ((ldq | ldk | ldv | ldo) % 4 != 0 || ldq < 64 * H || ldk < 64 * H || ldv < 64 * H || ldo < 64 * H || ldg < 64 * H ||
+      ldgv < 64 * H || !aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(dout))
+    return fail("mha_d64_bwd: q/k/v/dout must be 16-byte aligned with ld %% 4 == 0 and ld >= 64 H");
+  MhaD64Params a = {};
+  a.Q = q; a.K = k; a.V = v; a.dO = dout; a.P = p; a.delta = delta; a.delta_in = delta; a.dQ = dq; a.dK = dk; a.dV = dv;
+  a.B = B; a.H = H; a.S = S; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.ldgv = ldgv; a.scale = scale;
+  a.drop = stcat_make_drop(drop_p, drop_seed, drop_offset, drop_base);
+  STCAT_D64_PREPARE(mha_d64_bwd_dq_kernel);
+  STCAT_LAUNCH(mha_d64_bwd_dq_kernel, dim3(B * H, cdiv(S, 32)), dim3(256), mha_d64_dq_lds(S), (hipStream_t)stream, a);
+  if (int rc = launch_status()) return rc;
+  STCAT_D64_PREPARE(mha_d64_bwd_dkv_kernel);
+  STCAT_LAUNCH(mha_d64_bwd_dkv_kernel, dim3(B * H, cdiv(S, 32)), dim3(256), mha_d64_dkv_lds(S), (hipStream_t)stream, a);
   return launch_status();
 }
 

@@ -344,6 +344,81 @@ def linear_fwd_raw(x2d, w, bias, res2d=None, relu=False, out=None, ldy=None, c_g
     return out
 
 
+def gelu_raw(x, out=None):
+    """erf-GELU x / 2 (1 + erf(x / sqrt 2)) (stcat_ew op 12)"""
+    return ew(L.EW_GELU, x, out=out)
+
+
+def gelu_bwd_raw(dy, x, out=None):
+    return ew(L.EW_GELU_BWD, dy, x, out=out)
+
+
+def check_token_ids(ids: torch.Tensor, vocab: int, pos_ids: Optional[torch.Tensor] = None, max_pos: int = 0) -> None:
+    """Refuse token ids outside [0, vocab) (and position ids outside [0, max_pos)) before a kernel gathers with them.
+    Host tensors (what a tokenizer returns) cost nothing; a device tensor is read back (one synchronisation)."""
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= vocab:
+        raise L.StcatHipError(f"embed_ln: token id {hi if hi >= vocab else lo} is outside the vocabulary [0, {vocab})")
+    if pos_ids is not None:
+        lo, hi = int(pos_ids.min()), int(pos_ids.max())
+        if lo < 0 or hi >= max_pos:
+            raise L.StcatHipError(f"embed_ln: position id {hi if hi >= max_pos else lo} is outside the position table "
+                                  f"[0, {max_pos}): the text is too long")
+
+
+def embed_ln_fwd_raw(ids, pos_ids, word, pos, typ, gamma, beta, eps: float = 1e-5, drop=(0.0, 0, 0, None)):
+    """dropout(LayerNorm(word[ids] + pos[pos_ids] + typ[0])) -> (y [L,768], mean [L], rstd [L]); ids / pos_ids int64 [L]"""
+    _chk(word, pos, typ, gamma, beta)
+    check_token_ids(ids, word.shape[0], pos_ids, pos.shape[0])
+    n, D = ids.shape[0], word.shape[1]
+    y, mean, rstd = _empty(word, n, D), _empty(word, n), _empty(word, n)
+    L.call("stcat_embed_ln_fwd", ids.data_ptr(), pos_ids.data_ptr(), word.data_ptr(), pos.data_ptr(), typ.data_ptr(),
+           gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), n, D, word.shape[0],
+           pos.shape[0], eps, *drop, L.stream_of(word))
+    return y, mean, rstd
+
+
+def embed_ln_bwd_raw(dy, ids, pos_ids, word, pos, typ, gamma, mean, rstd, drop=(0.0, 0, 0, None), pad: int = -1):
+    """-> (dword [V,768], dpos [P,768], dtyp [1,768], dgamma, dbeta): table rows by a gather, no float atomics; row `pad`
+    of both tables (nn.Embedding's padding_idx) keeps a zero gradient"""
+    n, D = ids.shape[0], word.shape[1]
+    dy = _c(dy)
+    de = _empty(word, n, D)
+    dword, dpos, dtyp = _zeros(word, *word.shape), _zeros(word, *pos.shape), _zeros(word, *typ.shape)
+    dg, dbe = _zeros(word, D), _zeros(word, D)
+    L.call("stcat_embed_ln_bwd", dy.data_ptr(), ids.data_ptr(), pos_ids.data_ptr(), word.data_ptr(), pos.data_ptr(),
+           typ.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), de.data_ptr(), dword.data_ptr(),
+           dpos.data_ptr(), dtyp.data_ptr(), dg.data_ptr(), dbe.data_ptr(), n, D, word.shape[0], pos.shape[0], pad, *drop,
+           L.stream_of(word))
+    return dword, dpos, dtyp, dg, dbe
+
+
+def mha_d64_fwd_raw(q, k, v, kpm, scale: float = 0.125, drop=(0.0, 0, 0, None), keep: bool = True):
+    """head-dimension-64 attention on [B,S,64 H] tensors (S <= 128) -> (o, probabilities [B,H,S,S] | None)"""
+    B, S, D = v.shape
+    H = D // 64
+    _chk(q, k, v)
+    kp = _c(kpm.to(torch.uint8)) if kpm is not None else None
+    o = _empty(v, B, S, D)
+    P = _empty(v, B, H, S, S) if keep else None
+    L.call("stcat_mha_d64_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), L._ptr(P), B, H, S,
+           _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
+    return o, P
+
+
+def mha_d64_bwd_raw(q, k, v, do, P, scale: float = 0.125, drop=(0.0, 0, 0, None)):
+    """-> (dq, dk, dv), each [B,S,64 H]; every row has one writer (no atomics)"""
+    B, S, D = v.shape
+    H = D // 64
+    do = _c(do)
+    dq, dk, dv = _empty(v, B, S, D), _empty(v, B, S, D), _empty(v, B, S, D)
+    delta = _empty(v, B, H, S)
+    L.call("stcat_mha_d64_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(), P.data_ptr(), delta.data_ptr(),
+           dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, S, _ld3(q), _ld3(k), _ld3(v), D, D, D, scale, *drop,
+           L.stream_of(v))
+    return dq, dk, dv
+
+
 def _pad8(xs):
     xs = [L._ptr(x) for x in xs]
     return xs + [None] * (8 - len(xs))
@@ -507,7 +582,7 @@ def linear(x, w, b=None, res=None, relu=False):
 # LayerNorm(x + res)
 # ------------------------------------------------------------------------------------
 class LayerNormFn(Function):
-    """y = LayerNorm(res + dropout_p(x)) over 256 features (p = 0: plain x + res).  The residual branch's dropout
+    """y = LayerNorm(res + dropout_p(x)) over 256 (or, for the text encoder, 768) features (p = 0: plain x + res).  The residual branch's dropout
     (modal_encoder.py:237-240; query_decoder.py:344, 431, 436, 612, 653, 658) rides inside the kernel: mask from the
     counter stream in forward, regenerated in backward — no separate dropout pass over the activations."""
 

@@ -229,8 +229,10 @@ def _synth_value(name: str, shape: Tuple[int, ...]) -> np.ndarray:
             return (0.1 * u).astype(np.float32)
         if leaf == "running_var":
             return (1.0 + 0.5 * u).astype(np.float32)
-    if re.search(r"\.norm\d?$", parent) or parent.endswith(".norm"):
+    if re.search(r"\.norm\d?$", parent) or parent.endswith((".norm", ".LayerNorm", ".layer_norm")):
         return (1.0 + 0.1 * u if leaf == "weight" else 0.05 * u).astype(np.float32)
+    if parent.endswith("_embeddings"):  # the text encoder's word / position / token-type tables
+        return (0.05 * u).astype(np.float32)
     if len(shape) == 4:  # conv weights: kaiming-uniform, relu gain
         fan_in = shape[1] * shape[2] * shape[3]
         return (u * math.sqrt(6.0 / fan_in)).astype(np.float32)
