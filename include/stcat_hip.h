@@ -426,6 +426,15 @@ int stcat_rowscale(float* y, const float* w, long rows, int C, int period, void*
  * re-split; C % 8 == 0; plane modes only */
 int stcat_pl_rowscale(void* h, void* l, const float* w, long rows, int C, int period, void* stream);
 
+/* ---- ordered data-parallel gradient exchange (stcat_amd/dist.py) -------------------------------------------------
+ * The cross-rank sum as a fixed left-to-right chain: in holds n_ranks slices of n floats, slice k at in + k * stride;
+ *   acc = in[i];  acc = acc + in[k * stride + i] for k = 1 .. n_ranks - 1 (fp32, in exactly this order);  out[i] = acc * scale
+ * (one multiply after the last add).  n_ranks >= 1 (n_ranks == 1, scale == 1: a copy), n >= 0, stride >= n.  out may be
+ * exactly one of the slices (out == in + k * stride); any other overlap of out with a slice is refused.  16-byte aligned
+ * out / in with stride % 4 == 0 take the float4 path, anything else a scalar one.  No atomics: the same form in and out of
+ * deterministic mode. */
+int stcat_rank_sum(float* out, const float* in, int n_ranks, long n, long stride, float scale, void* stream);
+
 /* ---- VideoSTGLoss (models/criterion.py:11-208), all decoder layers in one launch --------------------------------
  * vec[k*nl + l] = un-weighted loss k of decoder layer l; k = 0 loss_bbox (criterion.py:38-55), 1 loss_giou (:56-66),
  * 2 loss_sted (:68-124), 3 loss_guided_attn (:126-145), 4 loss_actioness (:147-158; 0 when act == NULL).

@@ -117,6 +117,14 @@ def is_deterministic() -> bool:
     return _det_cache[1]
 
 
+def deterministic_requested() -> bool:
+    """is_deterministic() without loading the library: the loaded library's mode, else what STCAT_DETERMINISTIC sets it
+    to when the library is loaded (the library's own reading: anything but empty or 0)"""
+    if _lib is not None:
+        return is_deterministic()
+    return os.environ.get("STCAT_DETERMINISTIC", "") not in ("", "0")
+
+
 def f16_grad_scale() -> float:
     """factor carried by every GRADIENT plane in mode f16x3p (1.0 in every other mode): tools / op tests that build
     gradient planes themselves multiply by it; the product path scales where gradients enter the backbone (pl_act_bwd)"""

@@ -69,6 +69,7 @@
   X(stcat_map2d_pool_bwd_gather, "pppiiiis") \
   X(stcat_rowscale, "ppliis") \
   X(stcat_pl_rowscale, "pppliis") \
+  X(stcat_rank_sum, "ppillfs") \
   X(stcat_grad_sqnorm, "pppiips") \
   X(stcat_grad_sqnorm_ws, "pppiippls") \
   X(stcat_adamw_ema_step, "pppiipPPifffiffs") \

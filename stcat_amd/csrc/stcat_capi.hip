@@ -16,6 +16,7 @@
 #include "igemm_pl_as.h"
 #include "stem_pl.h"
 #include "pointwise.h"
+#include "rank_sum.h"
 #include "loss.h"
 #include "text_encoder.h"
 
@@ -2110,6 +2111,33 @@ int stcat_pl_rowscale(void* h, void* l, const float* w, long rows, int C, int pe
   if (g_mma_mode_raw < 4) return fail("pl_rowscale: plane modes only");
   STCAT_LAUNCH(pl_rowscale_kernel, dim3(grid_for(rows * (C / 8), 256, 8192)), dim3(256), 0, (hipStream_t)stream, (__bf16*)h,
                (__bf16*)l, w, rows, C, period, pl_np_arg());
+  return launch_status();
+}
+
+// The ordered cross-rank sum (rank_sum.h): out[i] = (in[i] + in[stride + i] + ... , left to right) * scale.
+int stcat_rank_sum(float* out, const float* in, int n_ranks, long n, long stride, float scale, void* stream) {
+  if (!out) return fail("rank_sum: out is null");
+  if (!in) return fail("rank_sum: in is null");
+  if (n_ranks < 1) return fail("rank_sum: n_ranks=%d (at least 1)", n_ranks);
+  if (n < 0) return fail("rank_sum: n=%ld is negative", n);
+  if (stride < n) return fail("rank_sum: stride=%ld is less than n=%ld (the slices would overlap)", stride, n);
+  if (n == 0) return 0;
+  // out may BE one of the slices (every thread reads all ranks of its element before it writes it); any other overlap
+  // with a slice would let one thread overwrite what another has yet to read
+  const uintptr_t o = reinterpret_cast<uintptr_t>(out), bytes = (uintptr_t)n * 4;
+  for (int k = 0; k < n_ranks; ++k) {
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in) + (uintptr_t)k * (uintptr_t)stride * 4;
+    if (o != s && o < s + bytes && s < o + bytes)
+      return fail("rank_sum: out overlaps slice %d of in without being that slice (out == in + k * stride is the only alias allowed)", k);
+  }
+  const bool vec = aligned16(out) && aligned16(in) && stride % 4 == 0;
+  // ~2048 workgroups of 256 lanes, grid-strided: 8 per CU keep the loads of 8 ranks x 16 B per lane in flight
+  if (vec)
+    STCAT_LAUNCH(rank_sum_kernel<true>, dim3(grid_for(n >> 2, 256, 2048)), dim3(256), 0, (hipStream_t)stream, out, in, n_ranks, n,
+                 stride, scale);
+  else
+    STCAT_LAUNCH(rank_sum_kernel<false>, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, out, in, n_ranks, n,
+                 stride, scale);
   return launch_status();
 }
 

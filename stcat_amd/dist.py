@@ -15,7 +15,12 @@ the reference model in torch DDP with find_unused_parameters=True).  Here instea
   ``ops.GRAD_SINK``) from its weight-gradient stream, and the buckets are laid out so that the LAST one to complete
   (layer2 + the tail of layer3) is small — what remains exposed after the last kernel of backward is one <= 16 MB
   all-reduce instead of a 128 MB one;
-* ``finish()`` waits for the collectives and applies the 1/world mean.
+* ``finish()`` waits for the collectives and applies the 1/world mean;
+* the ORDERED exchange (``ordered=True`` / ``STCAT_DP_ORDERED=1``; automatic in deterministic mode beyond two ranks): the
+  collectives only move bytes — an all-to-all brings every rank's copy of this rank's shard, ``stcat_rank_sum`` adds them
+  left to right in rank order (times 1/world), an all-gather hands the result round.  The order in which a collective
+  adds the ranks' values belongs to RCCL (algorithm per message size, topology, channel count); this one is fixed, so
+  every rank ends with the same bits, run after run.
 
 xGMI is point-to-point (7 links per GPU): few large messages beat many small ones, hence big buckets.
 ``torch.distributed`` backend "nccl" is RCCL on ROCm; the CPU test-suite drives the same class over gloo.
@@ -27,6 +32,9 @@ from typing import Dict, List, Optional
 
 import torch
 import torch.distributed as dist
+
+from . import _lib
+
 
 def init_rccl_process_group(device: torch.device, **kw) -> None:
     """`dist.init_process_group("nccl")` (= RCCL on ROCm) with the collectives on a HIGH-PRIORITY stream: HIP keeps a
@@ -53,11 +61,14 @@ def live_trainable(named_params):
 
 class GradBucketReducer:
     def __init__(self, model: torch.nn.Module, bucket_mb: float = 64.0, process_group=None, extra_numel: int = 0,
-                 force_comm: bool = False, tail_mb: float = 16.0):
+                 force_comm: bool = False, tail_mb: float = 16.0, ordered: Optional[bool] = None):
         """extra_numel: a dummy tail bucket (e.g. 124.6 M elements to emulate the reference's RoBERTa gradients
-        in the message size) — reduced with the rest, never read."""
+        in the message size) — reduced with the rest, never read.
+        ordered: the rank-ordered exchange (all-to-all, stcat_rank_sum, all-gather) instead of the summing collective;
+        None: STCAT_DP_ORDERED (1 / 0), else on exactly when world > 2 in deterministic mode."""
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
         # comm: gather into flat buckets and all-reduce.  force_comm keeps that path on with a single rank
         # (a 1-GPU box can then exercise the real RCCL calls; the mean over 1 rank is the identity)
         self.comm = self.world > 1 or (force_comm and dist.is_initialized())
@@ -108,6 +119,16 @@ class GradBucketReducer:
             raise ValueError(f"STCAT_DP_COLLECTIVE={self.collective!r}: expected allreduce or rs_ag")
         if self.collective == "rs_ag" and not self.avg_in_collective:
             self.collective = "allreduce"
+        # The ordered exchange replaces either of them (`collective` keeps its meaning: what runs when it is off).  A sum of
+        # two operands has one order, so up to two ranks nothing changes unless it is asked for; the question "is the mode
+        # on" is answered without loading the kernel library (a reducer over gloo on CPU tensors has none to load).
+        if ordered is None:
+            env = os.environ.get("STCAT_DP_ORDERED", "")
+            if env not in ("", "0", "1"):
+                raise ValueError(f"STCAT_DP_ORDERED={env!r}: expected 1 or 0")
+            ordered = (env == "1") if env else (self.world > 2 and _lib.deterministic_requested())
+        self.ordered = bool(ordered) and self.comm
+        self._exchange_stream = None     # the stream the ordered exchange is issued on (created with the first bucket)
         self._owner = {}
         pad_to = 64 * max(self.world, 1)      # a flat bucket splits into `world` equal, 256-byte aligned shards
         for bi, b in enumerate(self.buckets):
@@ -116,7 +137,9 @@ class GradBucketReducer:
             # the flat communication buffer only exists when there is somebody to talk to
             b["flat"] = torch.zeros(b["padded"], dtype=torch.float32, device=dev) if self.comm else None
             b["shard"] = (torch.empty(b["padded"] // self.world, dtype=torch.float32, device=dev)
-                          if (self.comm and self.collective == "rs_ag") else None)
+                          if (self.comm and self.collective == "rs_ag" and not self.ordered) else None)
+            # ordered exchange: where the all-to-all puts every rank's copy of this rank's shard (as large as the bucket)
+            b["recv"] = torch.empty(b["padded"], dtype=torch.float32, device=dev) if self.ordered else None
             # the reference's DDP also reduces the text encoder's 124.6 M gradients, which are complete right after the
             # encoder's backward — BEFORE the backbone's: the dummy message standing in for them is
             # launched behind the bucket that holds input_proj (the first thing after the encoder), not in finish()
@@ -138,7 +161,8 @@ class GradBucketReducer:
         extra_padded = -(-extra_numel // pad_to) * pad_to
         self.extra = torch.zeros(extra_padded, dtype=torch.float32, device=dev0) if (extra_numel and self.comm) else None
         self._extra_shard = (torch.empty(extra_padded // self.world, dtype=torch.float32, device=dev0)
-                             if (self.extra is not None and self.collective == "rs_ag") else None)
+                             if (self.extra is not None and self.collective == "rs_ag" and not self.ordered) else None)
+        self._extra_recv = torch.empty_like(self.extra) if (self.extra is not None and self.ordered) else None
         self._extra_work = None
         self.extra_numel = extra_numel
         self.skip_extra = False      # True: leave the dummy (text-encoder-sized) message out of the following steps
@@ -276,18 +300,50 @@ class GradBucketReducer:
                     v.zero_()
             if srcs:
                 torch._foreach_copy_(dsts, srcs)
-            b["work"] = self._reduce(b["flat"], b["shard"])
+            b["work"] = self._reduce(b["flat"], b["shard"], b["recv"])
             if b["triggers_extra"] and self.extra is not None and self._extra_work is None and not self.skip_extra:
-                self._extra_work = self._reduce(self.extra, self._extra_shard)
+                self._extra_work = self._reduce(self.extra, self._extra_shard, self._extra_recv)
         b["pending"] = -1
 
-    def _reduce(self, flat, shard):
-        """asynchronous mean (RCCL) / sum (gloo) of one flat buffer over the ranks, in place"""
+    def _reduce(self, flat, shard, recv=None):
+        """asynchronous mean (RCCL; ordered exchange) / sum (gloo) of one flat buffer over the ranks, in place"""
+        if self.ordered:
+            return self._exchange(flat, recv)
         op = dist.ReduceOp.AVG if self.avg_in_collective else dist.ReduceOp.SUM
         if shard is not None:
             dist.reduce_scatter_tensor(shard, flat, op=op, group=self.group, async_op=True)
             return dist.all_gather_into_tensor(flat, shard, group=self.group, async_op=True)   # same stream: ordered
         return dist.all_reduce(flat, op=op, group=self.group, async_op=True)
+
+    def _exchange(self, flat, recv):
+        """The ordered form of _reduce: shard r of `flat` (padded // world floats, 256-byte aligned) is this rank's to sum.
+        all_to_all_single brings every rank's copy of it into `recv`, slice k from rank k; stcat_rank_sum adds the slices
+        rank 0 first and scales by fp32(1 / world) — the same chain for every shard, whichever rank owns it — in place in
+        this rank's slice of `flat`; all_gather_into_tensor copies the shards round, so every rank holds the same bits.
+        On the GPU all of it is issued on the reducer's own exchange stream, ordered behind the current stream (which
+        _launch has ordered behind the delivering streams): the stream waits for the all-to-all (work.wait() is a stream
+        wait on RCCL), runs the sum and hands the all-gather to the collective's stream — no compute stream waits for
+        anything before finish().  (Over gloo, what the tests run, work.wait() also holds the host until the all-to-all is
+        done.)  The stream has the collectives' high priority: HIP serves each priority from its own
+        hardware queues (init_rccl_process_group), so it takes none of the step's four."""
+        S = flat.numel() // self.world
+        mine = flat[self.rank * S:(self.rank + 1) * S]
+        scale = 1.0 / self.world
+
+        def run():
+            dist.all_to_all_single(recv, flat, group=self.group, async_op=True).wait()
+            _lib.call("stcat_rank_sum", mine.data_ptr(), recv.data_ptr(), self.world, S, S, scale, _lib.stream_of(flat))
+            return dist.all_gather_into_tensor(flat, mine, group=self.group, async_op=True)
+
+        _lib.check_tensor(flat, "gradient bucket")
+        if not flat.is_cuda:
+            return run()
+        if self._exchange_stream is None:
+            self._exchange_stream = torch.cuda.Stream(flat.device, priority=-1)
+        ex = self._exchange_stream
+        ex.wait_stream(torch.cuda.current_stream(flat.device))
+        with torch.cuda.stream(ex):
+            return run()
 
     def _on_grad(self, p):
         # (the post-accumulate hook also fires for a parameter whose node returned None because it was handed over through
@@ -330,10 +386,10 @@ class GradBucketReducer:
             if self.deferred or b["pending"] >= 0:  # (eager) a parameter got no gradient: reduce what is there
                 self._launch(b)
         if self.extra is not None and self._extra_work is None and not self.skip_extra:   # (no bucket triggered it)
-            self._extra_work = self._reduce(self.extra, self._extra_shard)
+            self._extra_work = self._reduce(self.extra, self._extra_shard, self._extra_recv)
         for b in self.buckets:
             b["work"].wait()
-            if not self.avg_in_collective and self.world > 1:
+            if not self.avg_in_collective and not self.ordered and self.world > 1:
                 b["flat"].mul_(1.0 / self.world)
             for (n, p), v in zip(b["params"], b["views"]):
                 p.grad = v

@@ -230,10 +230,16 @@ class Recorder:
         # recording was REFUSED and the whole backbone node stayed on the eager path: +6 ms of host enqueue each way and
         # +3.4 ms per step at one rank, profiles/r06_prefix_pipeline.log — every N > 1 run since the watch became
         # unconditional in round 4 carried that.)
+        # For the same reason nothing the action launches through the library belongs in the plan: recording is suspended
+        # around it.  (The ordered exchange runs stcat_rank_sum from here; mirrored into the plan, every replay would run a
+        # stale copy of the sum with baked pointers at the yield point — racing the all-to-all that fills its input —
+        # besides the real one the action issues.)
         prev, self.allow_foreign = self.allow_foreign, True
+        rec, L.RECORDER = L.RECORDER, None
         try:
             return fn()
         finally:
+            L.RECORDER = rec
             self.allow_foreign = prev
 
     def effect(self, fn) -> None:
