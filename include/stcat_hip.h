@@ -94,6 +94,24 @@ int stcat_stem_fwd(const float* frames, const float* w, const float* scale, cons
  * normalisation, exactly as conv2d pads the normalised tensor.  4x fewer input bytes, no normalisation pass. */
 int stcat_stem_u8_fwd(const unsigned char* frames_hwc, const float* w, const float* in_scale, const float* in_shift,
                       const float* scale, const float* bias, float* y, int n, int H, int W, void* stream);
+/* The clip transforms of the input pipeline in one launch (datasets/transforms.py:57 hflip, :120 resize, :146 crop,
+ * :163 normalize; composed by datasets/build.py:20-64): a bilinear resize of a window of the source clip, written as
+ * fp32 [n,3,oh,ow] = a[c] * interp + b[c].
+ *   src       src_u8 != 0: uint8 [n,h,w,3] (decoder layout), interpolated on the raw 0..255 values;
+ *             src_u8 == 0: fp32 [n,3,h,w]
+ *   window    (win_y, win_x, win_h, win_w): the part of the source that is resized; taps clamp at ITS edges.  flip != 0
+ *             mirrors it: column j of the window reads source column win_x + win_w - 1 - j
+ *   (OH, OW)  the virtual output size: scales are win_h / OH and win_w / OW
+ *   (oy0, ox0, oh, ow)  the part of the virtual output that is computed and stored (a crop that follows a resize never
+ *             materialises the uncropped image; the taps still clamp at the whole window, as the uncropped resize's do)
+ *   antialias 0: torch upsample_bilinear2d, align_corners=False; 1: torch's separable triangle filter (width, then height)
+ *   a, b      per-channel device vectors [3]: 1/(255 std), -mean/std for a uint8 source, 1/std, -mean/std for a float one,
+ *             1/255 or 1 and 0 for an intermediate
+ * No atomics (the same in deterministic mode).  -1: empty window, window outside the source / the output, n <= 0, or a
+ * down-scale so strong that the smallest tile's source does not fit in LDS (a 1 x 4 tile: beyond about 40x). */
+int stcat_clip_resize(const void* src, int src_u8, int n, int h, int w, int win_y, int win_x, int win_h, int win_w,
+                      int flip, int OH, int OW, int oy0, int ox0, int oh, int ow, int antialias, const float* a,
+                      const float* b, float* out, void* stream);
 /* 3x3/2 pad 1 max-pool, NHWC (resnet maxpool) */
 int stcat_maxpool3x3s2(const float* x, float* y, int n, int H, int W, int C, void* stream);
 /* y = relu?(scale*conv(x,w) + bias + res), x NHWC [n,H,W,Cin], w OHWI [Cout,KH,KW,Cin]

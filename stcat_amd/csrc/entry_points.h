@@ -17,6 +17,7 @@
   X(stcat_frozen_bn_fold, "ppppppifs") \
   X(stcat_stem_fwd, "pppppiiis") \
   X(stcat_stem_u8_fwd, "pppppppiiis") \
+  X(stcat_clip_resize, "piiiiiiiiiiiiiiiippps") \
   X(stcat_maxpool3x3s2, "ppiiiis") \
   X(stcat_conv_fwd, "ppppppiiiiiiiiiis") \
   X(stcat_conv_dgrad, "pppppppppiiiiiiiiis") \

@@ -15,6 +15,7 @@
 #include "igemm_pl.h"
 #include "igemm_pl_as.h"
 #include "stem_pl.h"
+#include "clip_transform.h"
 #include "pointwise.h"
 #include "rank_sum.h"
 #include "loss.h"
@@ -849,6 +850,63 @@ int stcat_stem_u8_fwd(const unsigned char* frames_hwc, const float* w, const flo
   p.c_group = p.M; p.c_group_stride = 0; p.relu = 1;
   p.g = conv_geom_fwd(H, W, 3, 0, OH, OW, 7, 7, 2, 3);
   STCAT_LAUNCH(igemm_stem_kernel<true>, dim3(cdiv(p.M, 128)), dim3(256), 0, (hipStream_t)stream, p);
+  return launch_status();
+}
+
+int stcat_clip_resize(const void* src, int src_u8, int n, int h, int w, int win_y, int win_x, int win_h, int win_w,
+                      int flip, int OH, int OW, int oy0, int ox0, int oh, int ow, int antialias, const float* a,
+                      const float* b, float* out, void* stream) {
+  if (!src || !out || !a || !b) return fail("clip_resize: src, a, b and out are required");
+  if (n <= 0 || h <= 0 || w <= 0) return fail("clip_resize: bad source shape n=%d h=%d w=%d", n, h, w);
+  if (n > 65535) return fail("clip_resize: n=%d frames exceed one launch (65535)", n);
+  if (win_h <= 0 || win_w <= 0) return fail("clip_resize: empty clamp window %d x %d", win_h, win_w);
+  if (win_y < 0 || win_x < 0 || win_y > h - win_h || win_x > w - win_w)
+    return fail("clip_resize: clamp window (%d, %d, %d, %d) leaves the %d x %d source", win_y, win_x, win_h, win_w, h, w);
+  if (OH <= 0 || OW <= 0 || oh <= 0 || ow <= 0) return fail("clip_resize: empty output (%d, %d) / window %d x %d", OH, OW, oh, ow);
+  if (oy0 < 0 || ox0 < 0 || oy0 > OH - oh || ox0 > OW - ow)
+    return fail("clip_resize: output window (%d, %d, %d, %d) leaves the %d x %d output", oy0, ox0, oh, ow, OH, OW);
+  if (reinterpret_cast<size_t>(out) & 3 || (!src_u8 && reinterpret_cast<size_t>(src) & 3))
+    return fail("clip_resize: fp32 tensors must be 4-byte aligned");
+  ClipResizeParams p = {};
+  p.src = src; p.out = out; p.a = a; p.b = b;
+  p.src_bytes = (long)n * h * w * 3 * (src_u8 ? 1 : 4);
+  p.n = n; p.h = h; p.w = w; p.win_y = win_y; p.win_x = win_x; p.win_h = win_h; p.win_w = win_w; p.flip = flip ? 1 : 0;
+  p.OH = OH; p.OW = OW; p.oy0 = oy0; p.ox0 = ox0; p.oh = oh; p.ow = ow; p.antialias = antialias ? 1 : 0;
+  p.sy = (float)win_h / (float)OH;
+  p.sx = (float)win_w / (float)OW;
+  p.mty = clip_tap_cap(win_h, OH, p.antialias);
+  p.mtx = clip_tap_cap(win_w, OW, p.antialias);
+  // the largest tile whose staged source fits 64 KiB of LDS (two or more workgroups per CU); strong down-scales shrink it
+  // (tiles are 2^lgTH rows x 4 * 2^lgG - 4 columns: with the lanes' four columns cut at 16-byte boundaries of the output
+  // address, a row of the tile is 2^lgG lanes wide wherever it starts)
+  const int tiles[8][2] = {{4, 4}, {3, 4}, {3, 3}, {2, 3}, {2, 2}, {1, 2}, {1, 1}, {0, 1}};
+  long lds = 0;
+  for (auto& t : tiles) {
+    p.lgTH = t[0]; p.lgG = t[1];
+    p.TH = 1 << t[0]; p.TW = (4 << t[1]) - 4;
+    p.rcap = clip_span_cap(win_h, OH, p.antialias, p.TH);
+    p.ccap = clip_span_cap(win_w, OW, p.antialias, p.TW);
+    lds = clip_lds_floats(p) * 4;
+    if (lds <= 64 * 1024) break;
+  }
+  if (lds > 64 * 1024)
+    return fail("clip_resize: scales %d/%d x %d/%d need %ld bytes of LDS for the smallest tile (limit 65536)", win_h, OH,
+                win_w, OW, lds);
+  const long gy = cdiv(oh, p.TH);
+  if (gy > 65535) return fail("clip_resize: oh=%d exceeds one launch at this scale", oh);
+  const dim3 grid(cdiv(ow, p.TW), (unsigned)gy, n);
+#define STCAT_CLIP_LAUNCH(U8_, AA_) \
+  STCAT_LAUNCH((clip_resize_kernel<U8_, AA_>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, p)
+  if (src_u8 && p.antialias) {
+    STCAT_CLIP_LAUNCH(true, true);
+  } else if (src_u8) {
+    STCAT_CLIP_LAUNCH(true, false);
+  } else if (p.antialias) {
+    STCAT_CLIP_LAUNCH(false, true);
+  } else {
+    STCAT_CLIP_LAUNCH(false, false);
+  }
+#undef STCAT_CLIP_LAUNCH
   return launch_status();
 }
 

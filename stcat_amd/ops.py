@@ -1384,22 +1384,53 @@ PIXEL_MEAN, PIXEL_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)  # cfg.INPU
 _U8_NORM = {}
 
 
+def u8_norm(device, mean=PIXEL_MEAN, std=PIXEL_STD):
+    """(1 / (255 std), -mean / std) as fp32 device vectors: ToTensor + Normalize of a uint8 pixel as one multiply-add"""
+    key = (str(device), tuple(mean), tuple(std))
+    if key not in _U8_NORM:
+        m, s_ = torch.tensor(mean, dtype=torch.float64), torch.tensor(std, dtype=torch.float64)
+        _U8_NORM[key] = ((1.0 / (255.0 * s_)).float().to(device), (-m / s_).float().to(device))
+    return _U8_NORM[key]
+
+
 def stem_u8_fwd_raw(frames_u8_hwc, w_oihw, scale, bias, mean=PIXEL_MEAN, std=PIXEL_STD):
     """uint8 [n,H,W,3] decoder frames -> stem output NHWC fp32; ToTensor + Normalize fused into the gather
     (datasets/vidstg.py:140, datasets/transforms.py:155-168)."""
     n, H, W, C = frames_u8_hwc.shape
     assert C == 3 and frames_u8_hwc.dtype == torch.uint8 and frames_u8_hwc.is_contiguous()
     L.check_tensor(frames_u8_hwc)
-    key = (str(frames_u8_hwc.device), tuple(mean), tuple(std))
-    if key not in _U8_NORM:
-        m, s_ = torch.tensor(mean, dtype=torch.float64), torch.tensor(std, dtype=torch.float64)
-        _U8_NORM[key] = ((1.0 / (255.0 * s_)).float().to(frames_u8_hwc.device), (-m / s_).float().to(frames_u8_hwc.device))
-    isc, ish = _U8_NORM[key]
+    isc, ish = u8_norm(frames_u8_hwc.device, mean, std)
     OH, OW = conv_out_hw(H, W, 7, 2, 3)
     y = torch.empty(n, OH, OW, 64, device=frames_u8_hwc.device, dtype=_f32)
     L.call("stcat_stem_u8_fwd", frames_u8_hwc.data_ptr(), w_oihw.data_ptr(), isc.data_ptr(), ish.data_ptr(),
            scale.data_ptr(), bias.data_ptr(), y.data_ptr(), n, H, W, L.stream_of(frames_u8_hwc))
     return y
+
+
+def clip_resize_raw(src, a, b, out_size=None, *, window=None, flip=False, out_window=None, antialias=False, out=None):
+    """One launch of the clip-transform kernel (csrc/clip_transform.h; datasets/transforms.py:57,120,146,163).
+    src: uint8 [n,h,w,3] or fp32 [n,3,h,w], contiguous.  window = (y, x, h, w) of the source that is resized (default:
+    all of it; taps clamp at its edges), mirrored when flip.  out_size = (OH, OW), the virtual output (default: the
+    window's size); out_window = (y, x, h, w), the part of it that is computed (default: all).  Returns fp32
+    [n,3,oh,ow] = a[c] * interp + b[c]; `out`: a preallocated contiguous tensor of that shape."""
+    L.check_tensor(src)
+    u8 = src.dtype == torch.uint8
+    if u8:
+        n, h, w, c = src.shape
+    else:
+        assert src.dtype == _f32, src.dtype
+        n, c, h, w = src.shape
+    assert c == 3 and src.is_contiguous(), (tuple(src.shape), src.is_contiguous())
+    wy, wx, wh, ww = (0, 0, h, w) if window is None else window
+    OH, OW = (wh, ww) if out_size is None else out_size
+    oy, ox, oh, ow = (0, 0, OH, OW) if out_window is None else out_window
+    if out is None:
+        out = torch.empty(n, 3, max(oh, 0), max(ow, 0), device=src.device, dtype=_f32)
+    assert out.shape == (n, 3, oh, ow) and out.dtype == _f32 and out.is_contiguous(), tuple(out.shape)
+    assert a.dtype == _f32 and b.dtype == _f32 and a.numel() == 3 and b.numel() == 3
+    L.call("stcat_clip_resize", src.data_ptr(), int(u8), n, h, w, wy, wx, wh, ww, int(bool(flip)), OH, OW, oy, ox, oh, ow,
+           int(bool(antialias)), a.data_ptr(), b.data_ptr(), out.data_ptr(), L.stream_of(src))
+    return out
 
 
 def maxpool_raw(x):
