@@ -8,6 +8,8 @@ one autograd node per layer, gradient sums fused into the data-gradient epilogue
 kernel, packed in-projection gradients written straight into their row blocks.  The kernels (and the reference call
 sites they replace) are the ones of `stcat_amd.ops`; only the host-side wiring differs, so every parity test of the
 model covers this path.  The docstrings of the nodes below cite the reference lines they implement.
+Convention: a node calls the `*_fwd_raw` / `*_bwd_raw` pairs of `ops.py` (explicit arguments in, `(outputs, state)` out,
+`state` handed back to the backward half); the `Function` classes there are the op-by-op wrappers over the same pairs.
 """
 from __future__ import annotations
 
@@ -18,28 +20,6 @@ from torch.autograd import Function
 
 from . import _lib as L
 from . import ops, plans
-
-class _Ctx:
-    """the subset of the autograd ctx API that the Functions of stcat_amd.ops use"""
-
-    def __init__(self, needs_input_grad):
-        self.needs_input_grad = needs_input_grad
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts
-
-    def mark_non_differentiable(self, *a):
-        pass
-
-
-def _f(fn, nig, *args):
-    """run fn.forward outside autograd; returns (outputs, ctx)"""
-    c = _Ctx(nig)
-    return fn.forward(c, *args), c
-
-
-_T = (True,) * 8
 
 
 def _add(a, b):
@@ -235,22 +215,22 @@ class _Lane:
 # ------------------------------------------------------------------------------------------------------------------
 # shared sub-blocks
 # ------------------------------------------------------------------------------------------------------------------
-def _outln_f(a, Wo, bo, res, g, be, p):
-    """LayerNorm(res + dropout_p(a Wo^T + bo))  (modal_encoder.py:237-238, query_decoder.py:343-345, 431-432, 611-613, 653-654)"""
+def _outln_f(a, Wo, bo, res, g, be, p, eps=1e-5):
+    """LayerNorm(res + dropout_p(a Wo^T + bo))  (modal_encoder.py:237-238, query_decoder.py:343-345, 431-432, 611-613, 653-654;
+    the text encoder's RobertaSelfOutput / RobertaOutput)"""
     if p > 0.0:
         h, x_o = _lin_f(a, Wo, bo)
-        y, c_n = _f(ops.LayerNormFn, _T, h, res, g, be, 1e-5, p)
+        y, s_n = ops.layernorm_fwd_raw(h, res, g, be, eps, p)
     else:
         h, x_o = _lin_f(a, Wo, bo, res=res)          # eval: the residual rides in the GEMM epilogue
-        y, c_n = _f(ops.LayerNormFn, _T, h, None, g, be, 1e-5, 0.0)
-    return y, (c_n, x_o, Wo, p, y.shape)
+        y, s_n = ops.layernorm_fwd_raw(h, None, g, be, eps)
+    return y, (s_n, x_o, Wo, p)
 
 
 def _outln_b(st, dy, need_da=True, mask=None):
     """-> (d_a [M,K], d_res (shape of y), dWo, dbo, dg, dbe); mask: see _lin_b (the FFN's fused ReLU + dropout backward)"""
-    c_n, x_o, Wo, p, shp = st
-    r = ops.LayerNormFn.backward(c_n, dy.reshape(shp))
-    d_h, d_res, dg, dbe = r[0], r[1], r[2], r[3]
+    s_n, x_o, Wo, p = st
+    d_h, d_res, dg, dbe = ops.layernorm_bwd_raw(s_n, dy)
     if p == 0.0:
         d_res = d_h
     d_a, dWo, dbo, _ = _lin_b(d_h, x_o, Wo, need_dx=need_da, mask=mask)
@@ -312,50 +292,47 @@ def _ffn_f(x, W1, b1, W2, b2, g, be, p, pl=None):
             w1p, w1t, w2p, w2t = ent
             xp = ops.pl_split(x2)
             ymask = torch.empty(M, N // 8, device=x.device, dtype=torch.uint8)
-            seed, off, base = ops._dropout_stream.take(M * N, x.device) if p > 0.0 else (0, 0, None)
+            drop = ops._drop_args(p, M * N, x.device)
             st_x = L.stream_of(x2)
             # ... its result stays in planes: linear2 (K = 2048 -> 256) runs on the plane tile kernel, and the backward
             # pass reads the planes again (linear2's weight gradient); the fp32 [M, 2048] activation is never written
             hp = ops.Planes.empty(x, M, N)
             L.call("stcat_pl_linear_fwd", xp.h, xp.l, w1p.h, w1p.l, L._ptr(b1), None, None, hp.h, hp.l, ymask.data_ptr(),
-                   M, N, K, 1, float(p), seed, off, base, st_x)
+                   M, N, K, 1, *drop, st_x)
             D = W2.shape[0]
             res2 = x.reshape(M, D)
             res2 = res2 if res2.is_contiguous() else res2.contiguous()
             h2 = torch.empty(M, D, device=x.device, dtype=torch.float32)
             L.call("stcat_pl_linear_fwd", hp.h, hp.l, w2p.h, w2p.l, L._ptr(b2), res2.data_ptr() if p == 0.0 else None,
                    h2.data_ptr(), None, None, None, M, D, N, 0, 0.0, 0, 0, None, st_x)
-            y, c_n = _f(ops.LayerNormFn, _T, h2.view(*shp[:-1], D), x if p > 0.0 else None, g, be, 1e-5, p)
-            return y, ("planes", c_n, xp, hp, ymask, gv, (w1t, w2t), (W1, W2), p, y.shape)
+            y, s_n = ops.layernorm_fwd_raw(h2.view(*shp[:-1], D), x if p > 0.0 else None, g, be, 1e-5, p)
+            return y, ("planes", s_n, xp, hp, ymask, gv, (w1t, w2t), (W1, W2), p)
         if p > 0.0:
-            seed, off, base = ops._dropout_stream.take(M * N, x.device)
+            drop = ops._drop_args(p, M * N, x.device)
             f1d = torch.empty(M, N, device=x.device, dtype=torch.float32)
             L.call("stcat_linear_fwd_drop", x2.data_ptr(), W1.data_ptr(), L._ptr(b1), None, f1d.data_ptr(), M, N, K,
-                   x2.stride(0), N, 0, 1, float(p), seed, off, base, L.stream_of(x2))
+                   x2.stride(0), N, 0, 1, *drop, L.stream_of(x2))
         else:
             f1d = ops.linear_fwd_raw(x2, W1, b1, None, True)
         y, st = _outln_f(f1d.view(*shp[:-1], N), W2, b2, x, g, be, p)
         return y, (st, ("fused", 1.0 / (1.0 - p) if p > 0.0 else 1.0), x2, f1d, W1)
     f1, x_1 = _lin_f(x, W1, b1, relu=True)
-    c_dr = None
-    f1d = f1
-    if p > 0.0:
-        f1d, c_dr = _f(ops.DropoutFn, _T, f1, None, p)
+    f1d, s_dr = ops.dropout_fwd_raw(f1, None, p) if p > 0.0 else (f1, None)
     y, st = _outln_f(f1d, W2, b2, x, g, be, p)
-    return y, (st, c_dr, x_1, f1, W1)
+    return y, (st, s_dr, x_1, f1, W1)
 
 
 def _ffn_b(st, dy):
     """-> (d_x [M,D], dW1, db1, dW2, db2, dg, dbe)"""
     if st[0] == "planes":
         return _ffn_b_planes(st, dy)
-    st_o, c_dr, x_1, f1, W1 = st
-    if isinstance(c_dr, tuple) and c_dr[0] == "fused":
-        d_f1, d_x_res, dW2, db2, dg, dbe = _outln_b(st_o, dy, mask=(f1, c_dr[1]))     # f1 = dropout(relu(.)) here
+    st_o, s_dr, x_1, f1, W1 = st
+    if s_dr is not None and s_dr[0] == "fused":
+        d_f1, d_x_res, dW2, db2, dg, dbe = _outln_b(st_o, dy, mask=(f1, s_dr[1]))     # f1 = dropout(relu(.)) here
         d_x, dW1, db1, _ = _lin_b(d_f1, x_1, W1, add=d_x_res)
         return d_x, dW1, db1, dW2, db2, dg, dbe
     d_f1d, d_x_res, dW2, db2, dg, dbe = _outln_b(st_o, dy)
-    d_f1 = ops.DropoutFn.backward(c_dr, d_f1d.view(f1.shape))[0] if c_dr is not None else d_f1d
+    d_f1 = ops.dropout_bwd_raw(s_dr, d_f1d.view(f1.shape))[0] if s_dr is not None else d_f1d
     d_x, dW1, db1, _ = _lin_b(d_f1, x_1, W1, relu_y=f1, add=d_x_res)      # + residual gradient, fused into the dgrad
     return d_x, dW1, db1, dW2, db2, dg, dbe
 
@@ -365,9 +342,8 @@ def _ffn_b_planes(st, dy):
     gradient with the ReLU + dropout backward from the bit mask (A-stationary kernel, planes out) -> linear1's data gradient
     (plane tile kernel, K = 2048, fp32 out + the residual gradient); both weight gradients on the plane weight-gradient kernel,
     the bias gradients as column sums — all four on the weight-gradient stream."""
-    _, c_n, xp, hp, ymask, gv, (w1t, w2t), (W1, W2), p, shp = st
-    r = ops.LayerNormFn.backward(c_n, dy.reshape(shp))
-    d_h, d_res, dg, dbe = r[0], r[1], r[2], r[3]
+    _, s_n, xp, hp, ymask, gv, (w1t, w2t), (W1, W2), p = st
+    d_h, d_res, dg, dbe = ops.layernorm_bwd_raw(s_n, dy)
     if p == 0.0:
         d_res = d_h
     F, D = W1.shape
@@ -404,27 +380,6 @@ def _ffn_b_planes(st, dy):
     return d_x, dW1, db1, dW2, db2, dg, dbe
 
 
-def _ln_f(x, g, be, out=None):
-    M, D = x.shape
-    y = out if out is not None else torch.empty_like(x)
-    mean = ops._empty(x, M)
-    rstd = ops._empty(x, M)
-    L.call("stcat_layernorm_fwd", x.data_ptr(), None, g.data_ptr(), be.data_ptr(), y.data_ptr(), mean.data_ptr(),
-           rstd.data_ptr(), M, D, 1e-5, 0.0, 0, 0, None, L.stream_of(x))
-    return y, (x, g, mean, rstd)
-
-
-def _ln_b(st, dy, dg, dbe):
-    """dz; dg / dbe accumulate (the kernel adds into caller-zeroed buffers)"""
-    x, g, mean, rstd = st
-    M, D = x.shape
-    dy = dy if dy.is_contiguous() else dy.contiguous()
-    dz = torch.empty_like(x)
-    L.call("stcat_layernorm_bwd", dy.data_ptr(), x.data_ptr(), None, g.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-           dz.data_ptr(), None, dg.data_ptr(), dbe.data_ptr(), M, D, 0.0, 0, 0, None, L.stream_of(x))
-    return dz
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # encoder layer (modal_encoder.py:207-242), post-norm: 12 of them per step
 # ------------------------------------------------------------------------------------------------------------------
@@ -448,21 +403,19 @@ def _enc_layer_f(x, pos, kpm, p, nhead, W_in, B_in, Wo, bo, g1, be1, W1, b1, W2,
         qk_in = ops.ew(L.EW_ADD, x, pos_b if pos_b.is_contiguous() else pos_b.contiguous())      # q = k = src + pos :234
         qk, x_qk = _lin_f(qk_in, W_in[:2 * D], B_in[:2 * D])
     v, x_v = _lin_f(x, W_in[2 * D:], B_in[2 * D:])
-    (a, _), c_att = _f(ops.MhaSelfFn, (True, False, True) + (False,) * 5, qk, qk[:, :, D:], v, kpm,
-                       (D // nhead) ** -0.5, False, True, p)
+    (a, _), s_att = ops.mha_self_fwd_raw(qk, qk[:, :, D:], v, kpm, (D // nhead) ** -0.5, False, True, p, grads=True)
     x1, st1 = _outln_f(a, Wo, bo, x, g1, be1, p)
     y, st2 = _ffn_f(x1, W1, b1, W2, b2, g2, be2, p, pl=ffn_pl)
-    return y, (c_att, st1, st2, x_qk, x_v, D, shp, pos.shape, W_in)
+    return y, (s_att, st1, st2, x_qk, x_v, D, shp, pos.shape, W_in)
 
 
 def _enc_layer_b(st, dy, need_x, need_pos):
     """-> (d_x, d_pos | None, dW_in, dB_in, dWo, dbo, dg1, dbe1, dW1, db1, dW2, db2, dg2, dbe2); the weight gradients go
     through _wgrad: the caller opens the wgrad_batch"""
-    (c_att, st1, st2, x_qk, x_v, D, shp, pos_shape, W_in) = st
+    (s_att, st1, st2, x_qk, x_v, D, shp, pos_shape, W_in) = st
     d_x1, dW1, db1, dW2, db2, dg2, dbe2 = _ffn_b(st2, dy)
     d_a, d_x_res, dWo, dbo, dg1, dbe1 = _outln_b(st1, d_x1)
-    r = ops.MhaSelfFn.backward(c_att, d_a.view(shp), None)
-    dqk, dv = r[0], r[2]
+    dqk, _, dv = ops.mha_self_bwd_raw(s_att, d_a.view(shp), None)
     dW_in = ops._zeros(dy, 3 * D, D)        # packed in-projection gradient: the two GEMMs write its row blocks
     dB_in = ops._zeros(dy, 3 * D)
     d_x, _, _, _ = _lin_b(dv, x_v, W_in[2 * D:], need_dx=need_x, dw=dW_in[2 * D:], db=dB_in[2 * D:],
@@ -517,18 +470,18 @@ class TimeDecoderFn(Function):
             qk_in = ops.ew(L.EW_ADD, out, qpos_time)
             qk, st["x_qk"] = _lin_f(qk_in, W_in[:2 * D], B_in[:2 * D])
             v, st["x_v"] = _lin_f(out, W_in[2 * D:], B_in[2 * D:])
-            (a, w), st["att"] = _f(ops.MhaSelfFn, (True, False, True) + (False,) * 5, qk[None], qk[None][:, :, D:], v[None],
-                                   None, hd ** -0.5, True, True, p)                          # :604-610
+            (a, w), st["att"] = ops.mha_self_fwd_raw(qk[None], qk[None][:, :, D:], v[None], None, hd ** -0.5, True, True, p,
+                                                     grads=True)                             # :604-610
             ops.ew(L.EW_COPY, w, out=ws[i])
             tgt1, st["o1"] = _outln_f(a[0], Wo, bo, out, g1, be1, p)
             qc_in = ops.ew(L.EW_ADD, tgt1, query_pos)                                         # :633-634
             qc, st["x_qc"] = _lin_f(qc_in, W_c[:D], B_c[:D])
             kci, x_mp = _lin_f(mem_pos, W_c[D:2 * D], B_c[D:2 * D])
             vvi, x_mem = _lin_f(memory, W_c[2 * D:], B_c[2 * D:])
-            a2, st["q1"] = _f(ops.AttnQ1Fn, _T, qc, None, kci, None, vvi, kpm, hd ** -0.5, p)
+            a2, st["q1"] = ops.attn_q1_fwd_raw(qc, None, kci, None, vvi, kpm, hd ** -0.5, p)
             tgt2, st["o3"] = _outln_f(a2, Wo2, bo2, tgt1, g3, be3, p)                         # :653-654
             out, st["ffn"] = _ffn_f(tgt2, W1, b1, W2, b2, g4, be4, p)                         # :657-659
-            _, st["norm"] = _ln_f(out, gN, beN, out=hs[i])
+            _, st["norm"] = ops.layernorm_fwd_raw(out, None, gN, beN, 1e-5, out=hs[i])
             states.append(st)
         ctx.states = states
         ctx.prm = prm
@@ -566,13 +519,12 @@ class TimeDecoderFn(Function):
             st = ctx.states[i]
             (W_in, B_in, Wo, bo, g1, be1, W_c, B_c, Wo2, bo2, g3, be3, W1, b1, W2, b2, g4, be4) = \
                 prm[i * _NT_LAYER:(i + 1) * _NT_LAYER]
-            d_out = _ln_b(st["norm"], d_hs[i], dgN, dbeN)
+            d_out = ops.layernorm_bwd_raw(st["norm"], d_hs[i], dgN, dbeN)[0]     # (the shared norm: dgN / dbeN accumulate)
             if d_next is not None:
                 d_out = _add(d_out, d_next)
             d_tgt2, dW1, db1, dW2, db2, dg4, dbe4 = _ffn_b(st["ffn"], d_out)
             d_a2, d_tgt1_res, dWo2, dbo2, dg3, dbe3 = _outln_b(st["o3"], d_tgt2)
-            r = ops.AttnQ1Fn.backward(st["q1"], d_a2)
-            dqc, dkc, dvv = r[0], r[2], r[4]
+            dqc, _, dkc, _, dvv = ops.attn_q1_bwd_raw(st["q1"], d_a2)
             dW_c = ops._zeros(like, 3 * D, D)
             dB_c = ops._zeros(like, 3 * D)
             d_mp, _, _, _ = _lin_b(dkc, x_mp, W_c[D:2 * D], need_dx=need_mem, dw=dW_c[D:2 * D], db=dB_c[D:2 * D], add=d_mp)
@@ -581,8 +533,7 @@ class TimeDecoderFn(Function):
             d_qpos = d_qcin if d_qpos is None else _add(d_qpos, d_qcin)
             d_tgt1 = _add(d_tgt1_res.reshape(T, D), d_qcin)
             d_a, d_out_res, dWo, dbo, dg1, dbe1 = _outln_b(st["o1"], d_tgt1)
-            r = ops.MhaSelfFn.backward(st["att"], d_a.view(1, T, D), d_ws[i] if d_ws is not None else None)
-            dqk, dv = r[0], r[2]
+            dqk, _, dv = ops.mha_self_bwd_raw(st["att"], d_a.view(1, T, D), d_ws[i] if d_ws is not None else None)
             dW_in = ops._zeros(like, 3 * D, D)
             dB_in = ops._zeros(like, 3 * D)
             first = i == 0                               # layer 0's input state is the constant zero tensor
@@ -681,7 +632,7 @@ class BoxDecoderFn(Function):
              Wcqp, bcqp, Wqs, bqs, Wo2, bo2, g3, be3, W1, b1, W2, b2, g4, be4, Wmk, bmk, Wmp, bmp, Wmv, bmv) = lp
             first = i == 0
             st = {}
-            sine, st["sine"] = _f(ops.SineEmbedFn, _T, anchor)                                # [T,512]  :190
+            sine, st["sine"] = ops.sine_embed_fwd_raw(anchor)                                 # [T,512]  :190
             h_r, st["x_r1"] = _lin_f(sine, Wr1, br1, relu=True)                               # ref_point_head :191
             qpos, st["x_r2"] = _lin_f(h_r, Wr2, br2)
             st["h_r"] = h_r
@@ -715,7 +666,8 @@ class BoxDecoderFn(Function):
                 qp, _ = _lin_f(q, W_in[:D], B_in[:D])
                 kp_, _ = _lin_f(k, W_in[D:2 * D], B_in[D:2 * D])
                 vp, _ = _lin_f(v, W_in[2 * D:], B_in[2 * D:])
-            (a, _), st["att"] = _f(ops.MhaSelfFn, _T, qp[None], kp_[None], vp[None], None, hd ** -0.5, False, False, p)
+            (a, _), st["att"] = ops.mha_self_fwd_raw(qp[None], kp_[None], vp[None], None, hd ** -0.5, False, False, p,
+                                                     grads=True)
             tgt1, st["o1"] = _outln_f(a[0], Wo, bo, out, g1, be1, p)
             st["sa_in"] = (out, qpos, q, k, v)
             # ---- time-aligned cross-attention :355-432
@@ -735,7 +687,7 @@ class BoxDecoderFn(Function):
             lane.sync_main()                       # this layer's memory-side projections (queued a layer ago) are in
             if i + 1 < nl:
                 nxt = mem_proj(i + 1)              # ... the next layer's start now, beside the rest of this layer
-            a2, st["q1"] = _f(ops.AttnQ1Fn, _T, qc, qs, kci, kpi, vvi, kpm, (2 * hd) ** -0.5, p)
+            a2, st["q1"] = ops.attn_q1_fwd_raw(qc, qs, kci, kpi, vvi, kpm, (2 * hd) ** -0.5, p)
             tgt2, st["o3"] = _outln_f(a2, Wo2, bo2, tgt1, g3, be3, p)
             st["tgt1"] = tgt1
             out, st["ffn"] = _ffn_f(tgt2, W1, b1, W2, b2, g4, be4, p)                          # :435-437
@@ -749,7 +701,7 @@ class BoxDecoderFn(Function):
                 ops.ew(L.EW_SIGMOID, pre, out=refs[i + 1])
                 st["anchor"] = anchor
                 anchor = refs[i + 1]
-            _, st["norm"] = _ln_f(out, gN, beN, out=hs[i])                                   # :221-229
+            _, st["norm"] = ops.layernorm_fwd_raw(out, None, gN, beN, 1e-5, out=hs[i])       # :221-229
             states.append(st)
         ctx.states = states
         ctx.prm = prm
@@ -808,7 +760,7 @@ class BoxDecoderFn(Function):
             (Wqc, bqc, Wqp, bqp, Wqt, bqt, Wkc, bkc, Wkp, bkp, Wkt, bkt, Wv, bv, W_in, B_in, Wo, bo, g1, be1, Wcq, bcq,
              Wcqp, bcqp, Wqs, bqs, Wo2, bo2, g3, be3, W1, b1, W2, b2, g4, be4, Wmk, bmk, Wmp, bmp, Wmv, bmv) = lp
             first = i == 0
-            d_out = _ln_b(st["norm"], d_hs[i], dgN, dbeN)
+            d_out = ops.layernorm_bwd_raw(st["norm"], d_hs[i], dgN, dbeN)[0]     # (the shared norm: dgN / dbeN accumulate)
             if d_next is not None:
                 d_out = _add(d_out, d_next)
             if i != nl - 1 and d_refs is not None:
@@ -823,8 +775,7 @@ class BoxDecoderFn(Function):
             x_out, qpos, q, k, v = st["sa_in"]
             d_tgt2, dW1, db1, dW2, db2, dg4, dbe4 = _ffn_b(st["ffn"], d_out)
             d_a2, d_tgt1_res, dWo2, dbo2, dg3, dbe3 = _outln_b(st["o3"], d_tgt2)
-            r = ops.AttnQ1Fn.backward(st["q1"], d_a2)
-            dqc, dqs, dk1, dk2, dvv_i = r[0], r[1], r[2], r[3], r[4]
+            dqc, dqs, dk1, dk2, dvv_i = ops.attn_q1_bwd_raw(st["q1"], d_a2)
             d_mem, dWmk, dbmk, _ = _lin_b(dk1, x_mem, Wmk, need_dx=need_mem, add=d_mem)
             d_mem, dWmv, dbmv, _ = _lin_b(dvv_i, x_mem, Wmv, need_dx=need_mem, add=d_mem)
             _, dWmp, dbmp, _ = _lin_b(_add(dk1, dk2) if first else dk2, x_pos, Wmp, need_dx=False)
@@ -860,7 +811,7 @@ class BoxDecoderFn(Function):
                     d_qpos, dWcqp, dbcqp, _ = _lin_b(dqc, qpos, Wcqp)
                 d_tgt1, dWcq, dbcq, _ = _lin_b(dqc, st["tgt1"], Wcq, add=d_tgt1_res)
             d_a, d_out_res, dWo, dbo, dg1, dbe1 = _outln_b(st["o1"], d_tgt1)
-            r = ops.MhaSelfFn.backward(st["att"], d_a.view(1, T, D), None)
+            r = ops.mha_self_bwd_raw(st["att"], d_a.view(1, T, D), None)
             dW_in = ops._zeros(like, 3 * D, D)
             dB_in = ops._zeros(like, 3 * D)
             if mg:
@@ -907,7 +858,7 @@ class BoxDecoderFn(Function):
                                      need_dx=first and need_anchor)
             if first and need_anchor:
                 ops.ew2d(L.EW_ADD, d_sine[:, :D], d_sine_q, out=d_sine[:, :D])
-                d_a0 = ops.SineEmbedFn.backward(st["sine"], d_sine)
+                d_a0 = ops.sine_embed_bwd_raw(st["sine"], d_sine)
                 d_anchor = _add(d_anchor, d_a0) if d_anchor is not None else d_a0
                 if d_refs is not None:
                     d_anchor = _add(d_anchor, d_refs[0])
@@ -1089,11 +1040,11 @@ class TimeHeadsFn(Function):
                 st.append(None)
                 continue
             h, x1 = _lin_f(x, W1, b1, relu=True)
-            hd, c1 = (_f(ops.DropoutFn, _T, h, None, p) if p > 0.0 else (h, None))
+            hd, s1 = ops.dropout_fwd_raw(h, None, p) if p > 0.0 else (h, None)
             y, x2 = _lin_f(hd, W2, b2)
-            yd, c2 = (_f(ops.DropoutFn, _T, y, None, p) if p > 0.0 else (y, None))
+            yd, s2 = ops.dropout_fwd_raw(y, None, p) if p > 0.0 else (y, None)
             outs.append(yd.view(*shp[:-1], W2.shape[0]))
-            st.append((x1, h, c1, x2, c2, W1, W2))
+            st.append((x1, h, s1, x2, s2, W1, W2))
         ctx.st = st
         ctx.shp = shp
         ctx.set_materialize_grads(False)
@@ -1109,13 +1060,13 @@ class TimeHeadsFn(Function):
             if st is None or g is None:
                 grads += [None] * 4
                 continue
-            x1, h, c1, x2, c2, W1, W2 = st
+            x1, h, s1, x2, s2, W1, W2 = st
             g = g.contiguous().view(-1, W2.shape[0])
-            if c2 is not None:
-                g = ops.DropoutFn.backward(c2, g)[0]
+            if s2 is not None:
+                g = ops.dropout_bwd_raw(s2, g)[0]
             d_hd, dW2, db2, _ = _lin_b(g, x2, W2)
-            if c1 is not None:
-                d_hd = ops.DropoutFn.backward(c1, d_hd.view(h.shape))[0]
+            if s1 is not None:
+                d_hd = ops.dropout_bwd_raw(s1, d_hd.view(h.shape))[0]
             d_x, dW1, db1, _ = _lin_b(d_hd, x1, W1, relu_y=h, add=d_x)
             grads += [dW1, db1, dW2, db2]
         return (d_x.view(ctx.shp) if d_x is not None else None, None) + tuple(grads)

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -581,6 +582,57 @@ def linear(x, w, b=None, res=None, relu=False):
 # ------------------------------------------------------------------------------------
 # LayerNorm(x + res)
 # ------------------------------------------------------------------------------------
+def _stash(ctx, state, n: int) -> None:
+    """autograd side of a `*_raw` state: its first n fields are the tensors (saved with save_for_backward, outputs among
+    them, so the in-place checks keep working), the rest are plain facts kept on ctx"""
+    ctx.save_for_backward(*state[:n])
+    ctx.rest = tuple(state[n:])
+
+
+def _unstash(ctx, cls):
+    return cls(*ctx.saved_tensors, *ctx.rest)
+
+
+# (x2, r2: the [M, D] operands; drop: (p, seed, offset, base) of the residual branch's dropout)
+LayerNormState = namedtuple("LayerNormState", "x2 r2 gamma mean rstd drop xshape")
+
+
+def layernorm_fwd_raw(x, res, gamma, beta, eps, drop_p=0.0, out=None):
+    """-> (y, state); `out`: a contiguous buffer of x's size that receives y (the decoders write into hs[i])"""
+    shp = x.shape
+    D = shp[-1]
+    x2 = _c(x.reshape(-1, D))
+    r2 = _c(res.reshape(-1, D)) if res is not None else None
+    _chk(x2, r2, gamma, beta, out)
+    M = x2.shape[0]
+    assert out is None or (out.is_contiguous() and out.numel() == x2.numel()), "layernorm_fwd_raw: out= must be dense [M, D]"
+    y = out if out is not None else torch.empty_like(x2)
+    mean = _empty(x2, M)
+    rstd = _empty(x2, M)
+    drop = _drop_args(drop_p, x2.numel(), x2.device)
+    L.call("stcat_layernorm_fwd", x2.data_ptr(), L._ptr(r2), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+           mean.data_ptr(), rstd.data_ptr(), M, D, eps, *drop, L.stream_of(x2))
+    return y.view(shp), LayerNormState(x2, r2, gamma, mean, rstd, drop, shp)
+
+
+def layernorm_bwd_raw(st: LayerNormState, dy, dgamma=None, dbeta=None):
+    """-> (d_x, d_res | None, dgamma, dbeta).  The kernel ADDS the affine gradients into `dgamma` / `dbeta`: caller-zeroed
+    buffers that accumulate over several calls (the decoders' shared norm); not given, they are fresh zeros"""
+    x2, r2, gamma, mean, rstd, drop, xshape = st
+    M, D = x2.shape
+    g = _c(dy.reshape(M, D))
+    dz = torch.empty_like(x2)
+    dx = torch.empty_like(x2) if drop[0] > 0.0 else None
+    dgam = dgamma if dgamma is not None else _zeros(x2, D)
+    dbet = dbeta if dbeta is not None else _zeros(x2, D)
+    L.call("stcat_layernorm_bwd", g.data_ptr(), x2.data_ptr(), L._ptr(r2), gamma.data_ptr(), mean.data_ptr(),
+           rstd.data_ptr(), dz.data_ptr(), L._ptr(dx), dgam.data_ptr(), dbet.data_ptr(), M, D, *drop,
+           L.stream_of(g))
+    dzv = dz.view(xshape)
+    dxv = dx.view(xshape) if dx is not None else dzv
+    return dxv, (dzv if r2 is not None else None), dgam, dbet
+
+
 class LayerNormFn(Function):
     """y = LayerNorm(res + dropout_p(x)) over 256 (or, for the text encoder, 768) features (p = 0: plain x + res).  The residual branch's dropout
     (modal_encoder.py:237-240; query_decoder.py:344, 431, 436, 612, 653, 658) rides inside the kernel: mask from the
@@ -588,40 +640,13 @@ class LayerNormFn(Function):
 
     @staticmethod
     def forward(ctx, x, res, gamma, beta, eps, drop_p=0.0):
-        shp = x.shape
-        D = shp[-1]
-        x2 = _c(x.reshape(-1, D))
-        r2 = _c(res.reshape(-1, D)) if res is not None else None
-        _chk(x2, r2, gamma, beta)
-        M = x2.shape[0]
-        y = torch.empty_like(x2)
-        mean = _empty(x2, M)
-        rstd = _empty(x2, M)
-        drop = (0.0, 0, 0, None)
-        if drop_p > 0.0:
-            drop = (float(drop_p),) + _dropout_stream.take(x2.numel(), x2.device)
-        L.call("stcat_layernorm_fwd", x2.data_ptr(), L._ptr(r2), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
-               mean.data_ptr(), rstd.data_ptr(), M, D, eps, *drop, L.stream_of(x2))
-        ctx.save_for_backward(x2, r2, gamma, mean, rstd)
-        ctx.xshape = shp
-        ctx.drop = drop
-        return y.view(shp)
+        y, st = layernorm_fwd_raw(x, res, gamma, beta, eps, drop_p)
+        _stash(ctx, st, 5)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
-        x2, r2, gamma, mean, rstd = ctx.saved_tensors
-        M, D = x2.shape
-        g = _c(dy.reshape(M, D))
-        dz = torch.empty_like(x2)
-        dx = torch.empty_like(x2) if ctx.drop[0] > 0.0 else None
-        dgam = _zeros(x2, D)
-        dbet = _zeros(x2, D)
-        L.call("stcat_layernorm_bwd", g.data_ptr(), x2.data_ptr(), L._ptr(r2), gamma.data_ptr(), mean.data_ptr(),
-               rstd.data_ptr(), dz.data_ptr(), L._ptr(dx), dgam.data_ptr(), dbet.data_ptr(), M, D, *ctx.drop,
-               L.stream_of(g))
-        dzv = dz.view(ctx.xshape)
-        dxv = dx.view(ctx.xshape) if dx is not None else dzv
-        return dxv, (dzv if r2 is not None else None), dgam, dbet, None, None
+        return layernorm_bwd_raw(_unstash(ctx, LayerNormState), dy) + (None, None)
 
 
 def layer_norm(x, gamma, beta, res=None, eps: float = 1e-5, drop_p: float = 0.0):
@@ -745,29 +770,42 @@ def inverse_sigmoid(x):
     return UnaryFn.apply(x, L.EW_INVSIG, L.EW_INVSIG_BWD, False)
 
 
+SineEmbedState = namedtuple("SineEmbedState", "a2 shape")
+
+
+def sine_embed_fwd_raw(anchor):
+    """-> (embedding [..., 512], state)"""
+    a2 = _c(anchor.reshape(-1, 4))
+    _chk(a2)
+    M = a2.shape[0]
+    out = _empty(a2, M, 512)
+    L.call("stcat_sine_embed_fwd", a2.data_ptr(), dim_t(a2.device).data_ptr(), out.data_ptr(), M, L.stream_of(a2))
+    return out.view(*anchor.shape[:-1], 512), SineEmbedState(a2, anchor.shape)
+
+
+def sine_embed_bwd_raw(st: SineEmbedState, g):
+    """-> d_anchor"""
+    a2, shp = st
+    M = a2.shape[0]
+    g2 = _c(g.reshape(M, 512))
+    da = torch.empty_like(a2)
+    L.call("stcat_sine_embed_bwd", a2.data_ptr(), dim_t(a2.device).data_ptr(), g2.data_ptr(), da.data_ptr(), M,
+           L.stream_of(a2))
+    return da.view(shp)
+
+
 class SineEmbedFn(Function):
     """gen_sineembed_for_position — models/net_utils.py:29-56."""
 
     @staticmethod
     def forward(ctx, anchor):
-        a2 = _c(anchor.reshape(-1, 4))
-        _chk(a2)
-        M = a2.shape[0]
-        out = _empty(a2, M, 512)
-        L.call("stcat_sine_embed_fwd", a2.data_ptr(), dim_t(a2.device).data_ptr(), out.data_ptr(), M, L.stream_of(a2))
-        ctx.save_for_backward(a2)
-        ctx.shp = anchor.shape
-        return out.view(*anchor.shape[:-1], 512)
+        out, st = sine_embed_fwd_raw(anchor)
+        _stash(ctx, st, 1)
+        return out
 
     @staticmethod
     def backward(ctx, g):
-        (a2,) = ctx.saved_tensors
-        M = a2.shape[0]
-        g2 = _c(g.reshape(M, 512))
-        da = torch.empty_like(a2)
-        L.call("stcat_sine_embed_bwd", a2.data_ptr(), dim_t(a2.device).data_ptr(), g2.data_ptr(), da.data_ptr(), M,
-               L.stream_of(a2))
-        return da.view(ctx.shp)
+        return sine_embed_bwd_raw(_unstash(ctx, SineEmbedState), g)
 
 
 def sine_embed(anchor):
@@ -941,28 +979,48 @@ def dropout_keep_mask(seed: int, offset: int, n: int, p: float):
     return (z >> np.uint64(32)) >= np.uint64(thresh)
 
 
+def _drop_args(p: float, n: int, device):
+    """(p, seed, offset, base): the dropout arguments of a kernel, `n` counters of the step's dropout stream; p = 0 takes
+    none"""
+    if p > 0.0:
+        return (float(p),) + _dropout_stream.take(n, device)
+    return (0.0, 0, 0, None)
+
+
+DropoutState = namedtuple("DropoutState", "drop has_res")
+
+
+def dropout_fwd_raw(x, res, p):
+    """-> (res + dropout_p(x), state); p > 0 (the callers skip the launch otherwise)"""
+    x = _c(x)
+    r = _c(res) if res is not None else None
+    drop = (float(p),) + _dropout_stream.take(x.numel(), x.device)
+    y = torch.empty_like(x)
+    L.call("stcat_dropout", x.data_ptr(), L._ptr(r), y.data_ptr(), x.numel(), *drop, L.stream_of(x))
+    return y, DropoutState(drop, res is not None)
+
+
+def dropout_bwd_raw(st: DropoutState, g):
+    """-> (d_x, d_res | None): the same launch on dY (mask regenerated, never stored)"""
+    g = _c(g)
+    dx = torch.empty_like(g)
+    L.call("stcat_dropout", g.data_ptr(), None, dx.data_ptr(), g.numel(), *st.drop, L.stream_of(g))
+    return dx, (g if st.has_res else None)
+
+
 class DropoutFn(Function):
     """y = res + dropout_p(x) (res optional): nn.Dropout of modal_encoder.py:237-240, query_decoder.py:344, 431-436,
     612, 653-658, net_utils.py:24-25.  Backward = the same launch on dY (mask regenerated, never stored)."""
 
     @staticmethod
     def forward(ctx, x, res, p):
-        x = _c(x)
-        r = _c(res) if res is not None else None
-        seed, off, base = _dropout_stream.take(x.numel(), x.device)
-        y = torch.empty_like(x)
-        L.call("stcat_dropout", x.data_ptr(), L._ptr(r), y.data_ptr(), x.numel(), float(p), seed, off, base,
-               L.stream_of(x))
-        ctx.drop = (float(p), seed, off, base)
-        ctx.has_res = res is not None
+        y, st = dropout_fwd_raw(x, res, p)
+        _stash(ctx, st, 0)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        g = _c(g)
-        dx = torch.empty_like(g)
-        L.call("stcat_dropout", g.data_ptr(), None, dx.data_ptr(), g.numel(), *ctx.drop, L.stream_of(g))
-        return dx, (g if ctx.has_res else None), None
+        return dropout_bwd_raw(_unstash(ctx, DropoutState), g) + (None,)
 
 
 def dropout(x, p: float):
@@ -990,23 +1048,15 @@ def _ld3(t: torch.Tensor) -> int:
 # MFMAs per wave — measured +0.25 ms per C3 step (profiles/r05_as_kernel_experiments.log, item 8); it halves the
 # attention's activation memory, which is what it is kept for.
 MHA_RECOMPUTE = bool(os.environ.get("STCAT_MHA_RECOMPUTE"))
-MHA_BS6_MIN_ROWS = 128       # mode bf16x6p: rows up to this length stay on the fp32-pipe kernels (see MhaSelfFn.forward)
+MHA_BS6_MIN_ROWS = 128       # mode bf16x6p: rows up to this length stay on the fp32-pipe kernels (see mha_self_fwd_raw)
 # OPT-IN: gradient-carrying rows of 257..512 tokens on the bf16-pipe kernels as well (no S x S stash, no dS scratch).  Rows
 # above 512 tokens always train there; the default of this band is unchanged (fp32 long-row kernels).
 MHA_BS_LONG = os.environ.get("STCAT_MHA_BS_LONG", "0") not in ("", "0")
 
 
-def _mha_drop(drop_p: float, n: int, device):
-    """(p, seed, offset, base) of the dropout on the attention probabilities (nn.MultiheadAttention(dropout=p) in train
-    mode): `n` counters of the step's dropout stream; p = 0 takes none"""
-    if drop_p > 0.0:
-        return (float(drop_p),) + _dropout_stream.take(n, device)
-    return (0.0, 0, 0, None)
-
-
 def _mha_grads(v, packed_qk: bool):
-    """dq / dk / dv buffers of MhaSelfFn.backward -> (dq, dk, dv, leading dimension of dq and dk, the tuple backward
-    returns); a packed q|k projection gets ONE [B,S,2D] gradient, dq and dk are its column halves"""
+    """dq / dk / dv buffers of mha_self_bwd_raw -> (dq, dk, dv, leading dimension of dq and dk, the tuple it returns);
+    a packed q|k projection gets ONE [B,S,2D] gradient, dq and dk are its column halves"""
     B, S, D = v.shape
     if packed_qk:
         dqk = _empty(v, B, S, 2 * D)
@@ -1016,8 +1066,105 @@ def _mha_grads(v, packed_qk: bool):
         dk = _empty(v, B, S, D)
         ldg_qk = D
     dv = _empty(v, B, S, D)
-    ret = (dqk, None, dv) if packed_qk else (dq, dk, dv)
-    return dq, dk, dv, ldg_qk, ret + (None,) * 5
+    return dq, dk, dv, ldg_qk, ((dqk, None, dv) if packed_qk else (dq, dk, dv))
+
+
+# stat: the rows' softmax statistics (bs: the bf16-pipe kernels, rc: the fp32-pipe kernels that recompute the probabilities
+# in the backward), else the [B,H,SP,SP] probabilities; kp: key-padding bytes (bs / rc only: the probabilities hold the
+# padding already); drop: (p, seed, offset, base) of the dropout on the probabilities
+MhaSelfState = namedtuple("MhaSelfState", "q k v o stat kp scale drop bs rc packed_qk need_weights")
+
+
+def mha_self_fwd_raw(q, k, v, kpm, scale, need_weights, packed_qk, drop_p, grads: bool):
+    """-> ((out, head-mean weights | None), state | None).  `grads`: a backward will follow — it decides what the forward
+    keeps and, for rows of 257..512 tokens, which kernels run; without it there is no state."""
+    B, S, D = v.shape
+    H = D // 32
+    _chk(q, k, v)
+    kp = None
+    if kpm is not None:
+        kp = _c(kpm.to(torch.uint8))
+    SP = ((S + 31) // 32) * 32
+    o = _empty(v, B, S, D)
+    # bf16-pipe kernels (csrc/attention_bs.h): online softmax, any S, only the row log-sum-exp is kept for backward.
+    # The fp32-MFMA kernels remain for the exact-fp32 mode and for the one caller that consumes the head-mean
+    # weights (the time decoder's self-attention, T queries).
+    # Rows longer than 256 tokens (non-square clips) with gradients: the bf16-pipe backward has a streaming form for them
+    # (mha_bs_bwd_*_long_kernel: one 32-row tile per wave, the other operand through LDS in 128-row super-chunks; only
+    # the row log-sum-exp is kept).  Above 512 tokens it is the only training route — the fp32-pipe kernels stop there.
+    # For 256 < S <= 512 the DEFAULT stays the fp32 long-row kernels (S x S probability stash + a same-sized dS scratch:
+    # 2 x 210 MB per spatial layer at T = 64, S = 310); MHA_BS_LONG sends that band to the bf16-pipe kernels too.
+    # (round 6: mode bf16x6p runs here too — three planes per operand, six products: csrc/attention_bs.h, NP = 3; the
+    #  frozen experimental mode f16x3p keeps the fp32-pipe kernels; end to end the two pipes measured the same in that
+    #  mode, 76.41 / 76.56 against 76.34 / 76.57 ms per C3 step, profiles/r06_prefix_pipeline.log box E;
+    #  isolated kernel times: profiles/r06_attention.log)
+    # In bf16x6p only rows longer than 128 tokens take the six-product kernels (the encoder's spatial layers: 207 at C3):
+    # on the decoders' 64 queries and the temporal layers' 65 rows the fp32-pipe kernels are the faster ones — forward +
+    # backward 36.0 vs 42.5 us at S = 64, 45.0 vs 48.5 at S = 65 (isolated, profiles/r06_attention.log: three planes of
+    # 256 staged rows and 97 KB of LDS per workgroup do not pay on two or three tiles) — and those launches sit on the
+    # step's latency-bound chains.
+    mode = L.get_mma_mode()
+    bs = ((not need_weights) and mode not in ("f32", "f16x3p")
+          and (mode != "bf16x6p" or S > MHA_BS6_MIN_ROWS)
+          and (S <= 256 or S > 512 or MHA_BS_LONG or not grads))
+    if not bs and S > 512:
+        why = ("the head-mean attention weights are wanted" if need_weights else
+               f"mma mode {mode!r}" if mode in ("f32", "f16x3p") else
+               f"MHA_BS6_MIN_ROWS = {MHA_BS6_MIN_ROWS} keeps mode 'bf16x6p' off the bf16 pipe up to that row length")
+        raise ValueError(f"mha_self: {S} tokens per row, {why}: this call runs on the fp32-pipe attention kernels, which "
+                         "stop at 512 tokens per row; longer rows need mode bf16x3, bf16x3p or bf16x6p and no weights")
+    # dropout on the attention probabilities (nn.MultiheadAttention(dropout=p) in train mode)
+    drop = _drop_args(drop_p, B * H * SP * SP, v.device)
+
+    def state(stat, kp_, rc):
+        return MhaSelfState(q, k, v, o, stat, kp_, scale, drop, bs, rc, packed_qk, need_weights) if grads else None
+
+    if bs:
+        lse = _empty(v, B, H, S) if grads else None
+        L.call("stcat_mha_bs_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), L._ptr(lse),
+               B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
+        return (o, None), state(lse, kp, False)
+    # fp32-pipe kernels.  When nobody reads the head-mean weights and a row fits the short-row kernels, the forward keeps
+    # only (row maximum, 1 / row sum) and the backward recomputes its probability tiles (round 5): no S x S stash
+    if (not need_weights) and S <= 256 and MHA_RECOMPUTE and grads:
+        lse = _empty(v, B, H, SP, 2)
+        L.call("stcat_mha_self_fwd_lse", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), lse.data_ptr(),
+               B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
+        return (o, None), state(lse, kp, True)
+    # probabilities are kept only when somebody will read them: backward, or the head-mean weights
+    pt = _empty(v, B, H, SP, SP) if (need_weights or grads) else None
+    L.call("stcat_mha_self_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), L._ptr(pt),
+           B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
+    wts = None
+    if need_weights:
+        wts = _empty(v, B, S, S)
+        L.call("stcat_attn_weights_mean", pt.data_ptr(), wts.data_ptr(), B, H, S, *drop, L.stream_of(v))
+    return (o, wts), state(pt, None, False)
+
+
+def mha_self_bwd_raw(st: MhaSelfState, do, dwts):
+    """-> (dq | the packed [B,S,2D] dqk, dk | None when packed, dv); `dwts`: gradient of the head-mean weights or None"""
+    q, k, v, o = st.q, st.k, st.v, st.o
+    B, S, D = v.shape
+    H = D // 32
+    do = _c(do)
+    if st.bs or st.rc:      # both keep the row statistics only and share one argument list
+        dq, dk, dv, ldg_qk, ret = _mha_grads(v, st.packed_qk)
+        L.call("stcat_mha_bs_bwd" if st.bs else "stcat_mha_self_bwd_lse", q.data_ptr(), k.data_ptr(), v.data_ptr(),
+               L._ptr(st.kp), o.data_ptr(), do.data_ptr(), st.stat.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+               B, H, S, _ld3(q), _ld3(k), _ld3(v), D, ldg_qk, D, st.scale, *st.drop, L.stream_of(v))
+        return ret
+    pt = st.stat
+    dw = corr = None
+    if st.need_weights and dwts is not None:
+        dw = _c(dwts)
+        corr = _empty(v, B, H, S)
+    dst = torch.empty_like(pt)
+    dq, dk, dv, ldg_qk, ret = _mha_grads(v, st.packed_qk)
+    L.call("stcat_mha_self_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(),
+           pt.data_ptr(), L._ptr(dw), L._ptr(corr), dst.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+           B, H, S, _ld3(q), _ld3(k), _ld3(v), D, ldg_qk, D, st.scale, *st.drop, L.stream_of(v))
+    return ret
 
 
 class MhaSelfFn(Function):
@@ -1027,112 +1174,14 @@ class MhaSelfFn(Function):
 
     @staticmethod
     def forward(ctx, q, k, v, kpm, scale, need_weights, packed_qk, drop_p=0.0):
-        B, S, D = v.shape
-        H = D // 32
-        _chk(q, k, v)
-        kp = None
-        if kpm is not None:
-            kp = _c(kpm.to(torch.uint8))
-        SP = ((S + 31) // 32) * 32
-        o = _empty(v, B, S, D)
-        ctx.scale = scale
-        ctx.packed_qk = packed_qk
-        ctx.need_weights = need_weights
-        # bf16-pipe kernels (csrc/attention_bs.h): online softmax, any S, only the row log-sum-exp is kept for backward.
-        # The fp32-MFMA kernels remain for the exact-fp32 mode and for the one caller that consumes the head-mean
-        # weights (the time decoder's self-attention, T queries).
-        # Rows longer than 256 tokens (non-square clips) with gradients: the bf16-pipe backward has a streaming form for them
-        # (mha_bs_bwd_*_long_kernel: one 32-row tile per wave, the other operand through LDS in 128-row super-chunks; only
-        # the row log-sum-exp is kept).  Above 512 tokens it is the only training route — the fp32-pipe kernels stop there.
-        # For 256 < S <= 512 the DEFAULT stays the fp32 long-row kernels (S x S probability stash + a same-sized dS scratch:
-        # 2 x 210 MB per spatial layer at T = 64, S = 310); MHA_BS_LONG sends that band to the bf16-pipe kernels too.
-        # (round 6: mode bf16x6p runs here too — three planes per operand, six products: csrc/attention_bs.h, NP = 3; the
-        #  frozen experimental mode f16x3p keeps the fp32-pipe kernels; end to end the two pipes measured the same in that
-        #  mode, 76.41 / 76.56 against 76.34 / 76.57 ms per C3 step, profiles/r06_prefix_pipeline.log box E;
-        #  isolated kernel times: profiles/r06_attention.log)
-        # In bf16x6p only rows longer than 128 tokens take the six-product kernels (the encoder's spatial layers: 207 at C3):
-        # on the decoders' 64 queries and the temporal layers' 65 rows the fp32-pipe kernels are the faster ones — forward +
-        # backward 36.0 vs 42.5 us at S = 64, 45.0 vs 48.5 at S = 65 (isolated, profiles/r06_attention.log: three planes of
-        # 256 staged rows and 97 KB of LDS per workgroup do not pay on two or three tiles) — and those launches sit on the
-        # step's latency-bound chains.
-        mode = L.get_mma_mode()
-        grads = any(ctx.needs_input_grad[:3])
-        ctx.bs = ((not need_weights) and mode not in ("f32", "f16x3p")
-                  and (mode != "bf16x6p" or S > MHA_BS6_MIN_ROWS)
-                  and (S <= 256 or S > 512 or MHA_BS_LONG or not grads))
-        if not ctx.bs and S > 512:
-            why = ("the head-mean attention weights are wanted" if need_weights else
-                   f"mma mode {mode!r}" if mode in ("f32", "f16x3p") else
-                   f"MHA_BS6_MIN_ROWS = {MHA_BS6_MIN_ROWS} keeps mode 'bf16x6p' off the bf16 pipe up to that row length")
-            raise ValueError(f"mha_self: {S} tokens per row, {why}: this call runs on the fp32-pipe attention kernels, which "
-                             "stop at 512 tokens per row; longer rows need mode bf16x3, bf16x3p or bf16x6p and no weights")
-        ctx.rc = False
-        if ctx.bs:
-            keep = any(ctx.needs_input_grad[:3])
-            lse = _empty(v, B, H, S) if keep else None
-            drop = _mha_drop(drop_p, B * H * SP * SP, v.device)
-            L.call("stcat_mha_bs_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), L._ptr(lse),
-                   B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
-            ctx.drop = drop
-            if keep:
-                ctx.save_for_backward(q, k, v, o, lse, kp)
-            ctx.mark_non_differentiable()
-            return o, None
-        # fp32-pipe kernels.  When nobody reads the head-mean weights and a row fits the short-row kernels, the forward keeps
-        # only (row maximum, 1 / row sum) and the backward recomputes its probability tiles (round 5): no S x S stash
-        ctx.rc = (not need_weights) and S <= 256 and MHA_RECOMPUTE and any(ctx.needs_input_grad[:3])
-        if ctx.rc:
-            lse = _empty(v, B, H, SP, 2)
-            drop = _mha_drop(drop_p, B * H * SP * SP, v.device)
-            L.call("stcat_mha_self_fwd_lse", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), lse.data_ptr(),
-                   B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
-            ctx.drop = drop
-            ctx.save_for_backward(q, k, v, o, lse, kp)
-            ctx.mark_non_differentiable()
-            return o, None
-        # probabilities are kept only when somebody will read them: backward, or the head-mean weights
-        keep = need_weights or any(ctx.needs_input_grad[:3])
-        pt = _empty(v, B, H, SP, SP) if keep else None
-        drop = _mha_drop(drop_p, B * H * SP * SP, v.device)
-        L.call("stcat_mha_self_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kp), o.data_ptr(), L._ptr(pt),
-               B, H, S, _ld3(q), _ld3(k), _ld3(v), D, scale, *drop, L.stream_of(v))
-        wts = None
-        if need_weights:
-            wts = _empty(v, B, S, S)
-            L.call("stcat_attn_weights_mean", pt.data_ptr(), wts.data_ptr(), B, H, S, *drop, L.stream_of(v))
-        ctx.drop = drop
-        if keep:
-            ctx.save_for_backward(q, k, v, o, pt)
-        if need_weights:
-            return o, wts
-        ctx.mark_non_differentiable()
-        return o, None
+        outs, st = mha_self_fwd_raw(q, k, v, kpm, scale, need_weights, packed_qk, drop_p, any(ctx.needs_input_grad[:3]))
+        if st is not None:
+            _stash(ctx, st, 6)
+        return outs
 
     @staticmethod
     def backward(ctx, do, dwts):
-        do = _c(do)
-        if ctx.bs or ctx.rc:      # both keep the row statistics only and share one argument list
-            q, k, v, o, lse, kp = ctx.saved_tensors
-            B, S, D = v.shape
-            H = D // 32
-            dq, dk, dv, ldg_qk, ret = _mha_grads(v, ctx.packed_qk)
-            L.call("stcat_mha_bs_bwd" if ctx.bs else "stcat_mha_self_bwd_lse", q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                   L._ptr(kp), o.data_ptr(), do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                   B, H, S, _ld3(q), _ld3(k), _ld3(v), D, ldg_qk, D, ctx.scale, *ctx.drop, L.stream_of(v))
-            return ret
-        q, k, v, o, pt = ctx.saved_tensors
-        B, S, D = v.shape
-        H = D // 32
-        dw = corr = None
-        if ctx.need_weights and dwts is not None:
-            dw = _c(dwts)
-            corr = _empty(v, B, H, S)
-        dst = torch.empty_like(pt)
-        dq, dk, dv, ldg_qk, ret = _mha_grads(v, ctx.packed_qk)
-        L.call("stcat_mha_self_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(),
-               pt.data_ptr(), L._ptr(dw), L._ptr(corr), dst.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-               B, H, S, _ld3(q), _ld3(k), _ld3(v), D, ldg_qk, D, ctx.scale, *ctx.drop, L.stream_of(v))
-        return ret
+        return mha_self_bwd_raw(_unstash(ctx, MhaSelfState), do, dwts) + (None,) * 5
 
 
 def mha_self(q, k, v, kpm, scale, need_weights=False, drop_p=0.0):
@@ -1146,6 +1195,43 @@ def mha_self_packed(qk, v, kpm, scale, need_weights=False, drop_p=0.0):
     return MhaSelfFn.apply(qk, qk[:, :, D:], v, kpm, scale, need_weights, True, drop_p)
 
 
+AttnQ1State = namedtuple("AttnQ1State", "q1 q2 k1 k2 v P scale drop")
+
+
+def attn_q1_fwd_raw(q1, q2, k1, k2, v, kpm, scale, drop_p=0.0):
+    """-> (out [B,256], state)"""
+    B, S, D = v.shape
+    H = D // 32
+    q1, q2 = _c(q1), _c(q2)
+    _chk(q1, q2, k1, k2, v)
+    ldk, ldv = _ld3(k1), _ld3(v)  # k/v may be column slices of a wider (layer-batched) projection
+    assert k2 is None or _ld3(k2) == ldk
+    kp = _c(kpm.to(torch.uint8)) if kpm is not None else None
+    out = _empty(v, B, D)
+    P = _empty(v, B, H, S)
+    drop = _drop_args(drop_p, B * H * S, v.device)
+    L.call("stcat_attn_q1_fwd", q1.data_ptr(), L._ptr(q2), k1.data_ptr(), L._ptr(k2), v.data_ptr(), L._ptr(kp),
+           out.data_ptr(), P.data_ptr(), B, H, S, D, ldk, ldv, scale, *drop, L.stream_of(v))
+    return out, AttnQ1State(q1, q2, k1, k2, v, P, scale, drop)
+
+
+def attn_q1_bwd_raw(st: AttnQ1State, g):
+    """-> (dq1, dq2 | None, dk1, dk2 | None, dv)"""
+    q1, q2, k1, k2, v, P, scale, drop = st
+    B, S, D = v.shape
+    H = D // 32
+    g = _c(g)
+    dq1 = torch.empty_like(q1)
+    dq2 = torch.empty_like(q2) if q2 is not None else None
+    dk1 = _empty(v, B, S, D)
+    dk2 = _empty(v, B, S, D) if k2 is not None else None
+    dv = _empty(v, B, S, D)
+    L.call("stcat_attn_q1_bwd", q1.data_ptr(), L._ptr(q2), k1.data_ptr(), L._ptr(k2), v.data_ptr(), P.data_ptr(),
+           g.data_ptr(), dq1.data_ptr(), L._ptr(dq2), dk1.data_ptr(), L._ptr(dk2), dv.data_ptr(), B, H, S, D,
+           _ld3(k1), _ld3(v), scale, *drop, L.stream_of(v))
+    return dq1, dq2, dk1, dk2, dv
+
+
 class AttnQ1Fn(Function):
     """Time-aligned cross-attention, one query per frame (query_decoder.py:386-417 with the custom MHA
     of grounding_model/attention.py:184-393; query_decoder.py:618-639).
@@ -1153,40 +1239,13 @@ class AttnQ1Fn(Function):
 
     @staticmethod
     def forward(ctx, q1, q2, k1, k2, v, kpm, scale, drop_p=0.0):
-        B, S, D = v.shape
-        H = D // 32
-        q1, q2 = _c(q1), _c(q2)
-        _chk(q1, q2, k1, k2, v)
-        ldk, ldv = _ld3(k1), _ld3(v)  # k/v may be column slices of a wider (layer-batched) projection
-        assert k2 is None or _ld3(k2) == ldk
-        kp = _c(kpm.to(torch.uint8)) if kpm is not None else None
-        out = _empty(v, B, D)
-        P = _empty(v, B, H, S)
-        drop = (0.0, 0, 0, None)
-        if drop_p > 0.0:
-            drop = (float(drop_p),) + _dropout_stream.take(B * H * S, v.device)
-        ctx.drop = drop
-        L.call("stcat_attn_q1_fwd", q1.data_ptr(), L._ptr(q2), k1.data_ptr(), L._ptr(k2), v.data_ptr(), L._ptr(kp),
-               out.data_ptr(), P.data_ptr(), B, H, S, D, ldk, ldv, scale, *drop, L.stream_of(v))
-        ctx.save_for_backward(q1, q2, k1, k2, v, P)
-        ctx.scale = scale
+        out, st = attn_q1_fwd_raw(q1, q2, k1, k2, v, kpm, scale, drop_p)
+        _stash(ctx, st, 6)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        q1, q2, k1, k2, v, P = ctx.saved_tensors
-        B, S, D = v.shape
-        H = D // 32
-        g = _c(g)
-        dq1 = torch.empty_like(q1)
-        dq2 = torch.empty_like(q2) if q2 is not None else None
-        dk1 = _empty(v, B, S, D)
-        dk2 = _empty(v, B, S, D) if k2 is not None else None
-        dv = _empty(v, B, S, D)
-        L.call("stcat_attn_q1_bwd", q1.data_ptr(), L._ptr(q2), k1.data_ptr(), L._ptr(k2), v.data_ptr(), P.data_ptr(),
-               g.data_ptr(), dq1.data_ptr(), L._ptr(dq2), dk1.data_ptr(), L._ptr(dk2), dv.data_ptr(), B, H, S, D,
-               _ld3(k1), _ld3(v), ctx.scale, *ctx.drop, L.stream_of(v))
-        return dq1, dq2, dk1, dk2, dv, None, None, None
+        return attn_q1_bwd_raw(_unstash(ctx, AttnQ1State), g) + (None, None, None)
 
 
 def attn_q1(q1, q2, k1, k2, v, kpm, scale, drop_p=0.0):

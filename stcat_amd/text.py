@@ -64,32 +64,6 @@ def config_for(name: str) -> TextConfig:
 _N_EMB, _N_LAYER = 5, 16
 
 
-def _ln_f(x, res, g, be, eps, p):
-    return C._f(ops.LayerNormFn, C._T, x, res, g, be, eps, p)
-
-
-def _outln_f(a, W, b, res, g, be, eps, p):
-    """LayerNorm(res + dropout_p(a W^T + b)): RobertaSelfOutput / RobertaOutput"""
-    if p > 0.0:
-        h, x_o = C._lin_f(a, W, b)
-        y, c_n = _ln_f(h, res, g, be, eps, p)
-    else:
-        h, x_o = C._lin_f(a, W, b, res=res)          # eval: the residual rides in the GEMM epilogue
-        y, c_n = _ln_f(h, None, g, be, eps, 0.0)
-    return y, (c_n, x_o, W, p)
-
-
-def _outln_b(st, dy):
-    """-> (d_a, d_res, dW, db, dg, dbe)"""
-    c_n, x_o, W, p = st
-    r = ops.LayerNormFn.backward(c_n, dy)
-    d_h, d_res, dg, dbe = r[0], r[1], r[2], r[3]
-    if p == 0.0:
-        d_res = d_h
-    d_a, dW, db, _ = C._lin_b(d_h, x_o, W)
-    return d_a, d_res, dW, db, dg, dbe
-
-
 def _layer_f(x, kpm, H, eps, p, keep, Wq, bq, Wk, bk, Wv, bv, Wo, bo, g1, be1, Wi, bi, Wo2, bo2, g2, be2):
     """one RobertaLayer on x [S,768] (post-LN): self-attention, output + norm, GELU FFN + norm"""
     S, D = x.shape
@@ -102,13 +76,13 @@ def _layer_f(x, kpm, H, eps, p, keep, Wq, bq, Wk, bk, Wv, bv, Wo, bo, g1, be1, W
     att = ops._empty(x, S, D)
     P = ops._empty(x, H, S, S) if keep else None
     SP = ((S + 31) // 32) * 32
-    drop = ops._mha_drop(p, H * SP * SP, x.device)
+    drop = ops._drop_args(p, H * SP * SP, x.device)
     L.call("stcat_mha_d64_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), L._ptr(kpm), att.data_ptr(), L._ptr(P), 1, H, S,
            D, D, D, D, 0.125, *drop, L.stream_of(x))
-    h1, st1 = _outln_f(att, Wo, bo, x, g1, be1, eps, p)
+    h1, st1 = C._outln_f(att, Wo, bo, x, g1, be1, p, eps)
     i1, x_i = C._lin_f(h1, Wi, bi)
     a1 = ops.ew(L.EW_GELU, i1)
-    y, st2 = _outln_f(a1, Wo2, bo2, h1, g2, be2, eps, p)
+    y, st2 = C._outln_f(a1, Wo2, bo2, h1, g2, be2, p, eps)
     return y, (x, q, k, v, P, drop, H, st1, x_i, i1, st2, (Wq, Wk, Wv, Wi), multi)
 
 
@@ -116,10 +90,10 @@ def _layer_b(st, dy, need_x):
     """-> (d_x | None, the 16 parameter gradients in parameter order)"""
     x, q, k, v, P, drop, H, st1, x_i, i1, st2, (Wq, Wk, Wv, Wi), multi = st
     S, D = x.shape
-    d_a1, d_h1r, dWo2, dbo2, dg2, dbe2 = _outln_b(st2, dy)
+    d_a1, d_h1r, dWo2, dbo2, dg2, dbe2 = C._outln_b(st2, dy)
     d_i1 = ops.ew(L.EW_GELU_BWD, d_a1, i1)
     d_h1, dWi, dbi, _ = C._lin_b(d_i1, x_i, Wi, add=d_h1r)
-    d_att, d_xr, dWo, dbo, dg1, dbe1 = _outln_b(st1, d_h1)
+    d_att, d_xr, dWo, dbo, dg1, dbe1 = C._outln_b(st1, d_h1)
     d_att = d_att if d_att.is_contiguous() else d_att.contiguous()
     dq, dk, dv = ops._empty(x, S, D), ops._empty(x, S, D), ops._empty(x, S, D)
     delta = ops._empty(x, H, S)
@@ -161,7 +135,7 @@ class TextEncoderFn(Function):
         like = eg
         keep = (not frozen) and any(ctx.needs_input_grad)
         ctx.set_materialize_grads(False)      # an output nobody consumed (the grounding model ignores cls) costs nothing
-        drop_e = (float(p),) + ops._dropout_stream.take(S * D, dev) if p > 0.0 else (0.0, 0, 0, None)
+        drop_e = ops._drop_args(p, S * D, dev)
         x = ops._empty(like, S, D)
         mean, rstd = ops._empty(like, S), ops._empty(like, S)
         L.call("stcat_embed_ln_fwd", ids.data_ptr(), pos_ids.data_ptr(), word.data_ptr(), pos.data_ptr(), typ.data_ptr(),
@@ -179,12 +153,12 @@ class TextEncoderFn(Function):
         outs, tails = [], []
         for t in (x, pooled):
             h, x_r = C._lin_f(t, Wr, br)
-            y, c_n = _ln_f(h, None, gr, ber, 1e-12, 0.0)
-            c_d = None
+            y, s_n = ops.layernorm_fwd_raw(h, None, gr, ber, 1e-12)
+            s_d = None
             if p > 0.0:
-                y, c_d = C._f(ops.DropoutFn, C._T, y, None, p)
+                y, s_d = ops.dropout_fwd_raw(y, None, p)
             outs.append(y)
-            tails.append((x_r, c_n, c_d))
+            tails.append((x_r, s_n, s_d))
         ctx.save_for_backward(ids, pos_ids, mean, rstd, pooled, *prm)
         ctx.misc = (states, tails, x_p, drop_e, nl, eps, frozen, pad)
         return outs[0], outs[1]
@@ -204,14 +178,14 @@ class TextEncoderFn(Function):
             dWr, dbr = ops._zeros(like, *Wr.shape), ops._zeros(like, Wr.shape[0])
             dgr = dber = None
             d_in = []
-            for (x_r, c_n, c_d), g in zip(tails, (d_mem, d_cls)):
+            for (x_r, s_n, s_d), g in zip(tails, (d_mem, d_cls)):
                 if g is None:
                     d_in.append(None)
                     continue
                 g = g if g.is_contiguous() else g.contiguous()
-                if c_d is not None:
-                    g = ops.DropoutFn.backward(c_d, g)[0]
-                r = ops.LayerNormFn.backward(c_n, g)
+                if s_d is not None:
+                    g = ops.dropout_bwd_raw(s_d, g)[0]
+                r = ops.layernorm_bwd_raw(s_n, g)
                 dgr = r[2] if dgr is None else ops.ew(L.EW_ADD, dgr, r[2], out=dgr)
                 dber = r[3] if dber is None else ops.ew(L.EW_ADD, dber, r[3], out=dber)
                 d_t, _, _, _ = C._lin_b(r[0], x_r, Wr, need_dx=not frozen, dw=dWr, db=dbr)

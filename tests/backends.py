@@ -134,6 +134,15 @@ def use_hip():
     return torch.device("cuda:0")
 
 
+@contextlib.contextmanager
+def deterministic(on=True):
+    L.set_deterministic(on)
+    try:
+        yield
+    finally:
+        L.set_deterministic(False)
+
+
 def both(fn):
     """Register fn(dev, big) twice: test_emu_<name> (CPU, emulator) and test_gpu_<name> (marked gpu)."""
     import sys

@@ -18,19 +18,10 @@ import torch
 from stcat_amd import _lib as L
 from stcat_amd import ops, plans, synth
 from stcat_amd.misc import BoxList
-from tests.backends import both, close, host_memory_slot, use_emu, use_hip
+from tests.backends import both, close, deterministic, host_memory_slot, use_emu, use_hip
 from tests.test_ops import TOL, rnd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@contextlib.contextmanager
-def deterministic(on=True):
-    L.set_deterministic(on)
-    try:
-        yield
-    finally:
-        L.set_deterministic(False)
 
 
 @contextlib.contextmanager

@@ -2,7 +2,7 @@
 mha_bs_bwd_dkv_long_kernel — one 32-row tile per wave, the other operand streamed through LDS in 128-row super-chunks,
 probabilities rebuilt from the row log-sum-exp, no atomics and no workspace).
 
-Routing (ops.MhaSelfFn): rows above 512 tokens with gradients always take these kernels in the modes whose forward runs on
+Routing (ops.mha_self_fwd_raw): rows above 512 tokens with gradients always take these kernels in the modes whose forward runs on
 the bf16 pipe; 256 < S <= 512 keeps the fp32 long-row kernels unless ops.MHA_BS_LONG (STCAT_MHA_BS_LONG=1) is set.
 
 Op level (`@both`: host emulator and GPU): shapes / masks / packing against the fp32 PyTorch reference at the bar of

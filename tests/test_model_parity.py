@@ -928,7 +928,7 @@ def test_gpu_square_clip_with_padding_mask():
 @pytest.mark.gpu
 def test_gpu_nonsquare_clip_throughput_mode():
     """the same 405 x 720 clip in the 16-bit throughput mode: rows longer than 256 tokens train through the fp32 long-row
-    attention kernels there too (ops.MhaSelfFn); forward + loss + backward, family caps on the gradients"""
+    attention kernels there too (ops.mha_self_fwd_raw); forward + loss + backward, family caps on the gradients"""
     dev = use_hip()
     _compare(_hip_case(dev, "NS8_ragged", mma=THROUGHPUT_MMA), Ref.fixture("NS8_ragged"),
              grad_caps={k: min(4 * v, 5e-2) for k, v in GRAD_CAPS_16BIT.items()})  # (T = 8: few samples per gradient)

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 
 from stcat_amd import _lib as L
 from stcat_amd import ops
-from tests.backends import both, close
+from tests.backends import both, close, deterministic
 
 TOL = 2e-4
 
@@ -939,6 +939,121 @@ def _dropout(dev, big):
         _mha_dropout_case(dev, 16, 207, 8, need_w=False)
         _mha_dropout_case(dev, 1, 64, 8, need_w=True)
         _q1_dropout_case(dev, 64, 206, 8)
+
+def _same_bits(got, want, what):
+    """torch.equal, tensor by tensor (None only against None)"""
+    got = got if isinstance(got, (tuple, list)) else (got,)
+    want = want if isinstance(want, (tuple, list)) else (want,)
+    assert len(got) == len(want), what
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert (a is None) == (b is None), f"{what}[{i}]: {a is None} / {b is None}"
+        assert a is None or torch.equal(a, b), f"{what}[{i}] differs"
+
+
+@both
+def _raw_pairs_equal_autograd(dev, big):
+    """The `*_fwd_raw` / `*_bwd_raw` pairs of ops.py (what the composite nodes call) and the autograd wrappers over them are
+    the same computation: every output and every gradient torch.equal on equal inputs.  Deterministic mode, because the
+    LayerNorm affine gradients are float atomics otherwise."""
+    def leaves(*ts):
+        return [t.clone().requires_grad_(True) if t is not None else None for t in ts]
+
+    def restart():          # both runs of a case draw the same dropout counters
+        ops.manual_seed(7)
+        ops.dropout_begin_step(dev)
+
+    with deterministic():
+        # ---- LayerNorm (a): residual + dropout
+        x, r, gy = (rnd(5, 256, seed=s).to(dev) for s in (1, 2, 5))
+        g, b = (rnd(256, seed=3) * 0.1 + 1).to(dev), (rnd(256, seed=4) * 0.1).to(dev)
+        xa, ra, ga, ba = leaves(x, r, g, b)
+        restart()
+        y = ops.layer_norm(xa, ga, ba, res=ra, drop_p=0.2)
+        y.backward(gy)
+        restart()
+        y2, st = ops.layernorm_fwd_raw(x, r, g, b, 1e-5, 0.2)
+        _same_bits(y2, y.detach(), "layernorm (a) y")
+        _same_bits(ops.layernorm_bwd_raw(st, gy), (xa.grad, ra.grad, ga.grad, ba.grad), "layernorm (a) gradients")
+        assert not torch.equal(xa.grad, ra.grad)                       # the dropout did act
+        # ---- LayerNorm (b): no residual, y into a caller's buffer, affine gradients added into pre-filled buffers
+        xa, ga, ba = leaves(x, g, b)
+        y = ops.layer_norm(xa, ga, ba)
+        y.backward(gy)
+        buf = torch.zeros(2, 5, 256, device=dev)
+        y2, st = ops.layernorm_fwd_raw(x, None, g, b, 1e-5, out=buf[1])
+        assert y2.data_ptr() == buf[1].data_ptr() and not bool(buf[0].any())
+        _same_bits(buf[1], y.detach(), "layernorm (b) y")
+        pre_g, pre_b = rnd(256, seed=6).to(dev), rnd(256, seed=7).to(dev)
+        dg, db = pre_g.clone(), pre_b.clone()
+        d_x, d_res, dg2, db2 = ops.layernorm_bwd_raw(st, gy, dg, db)
+        assert d_res is None and dg2 is dg and db2 is db
+        _same_bits(d_x, xa.grad, "layernorm (b) dx")
+        _same_bits((dg, db), (ops.ew(L.EW_ADD, pre_g, ga.grad), ops.ew(L.EW_ADD, pre_b, ba.grad)), "layernorm (b) accumulate")
+        # ---- dropout, with and without the residual
+        x, r, gy = (rnd(3, 256, seed=s).to(dev) for s in (1, 2, 3))
+        for res in (r, None):
+            xa, ra = leaves(x, res)
+            restart()
+            y = ops.dropout_add(xa, ra, 0.5) if res is not None else ops.dropout(xa, 0.5)
+            y.backward(gy)
+            restart()
+            y2, st = ops.dropout_fwd_raw(x, res, 0.5)
+            _same_bits(y2, y.detach(), "dropout y")
+            _same_bits(ops.dropout_bwd_raw(st, gy), (xa.grad, ra.grad if res is not None else None), "dropout gradients")
+        # ---- self-attention: packed q|k on the current mode's route; head-mean weights with their gradient; unpacked + mask
+        scale, D = 32 ** -0.5, 64
+        qk, v, go = rnd(2, 37, 2 * D, seed=1).to(dev), rnd(2, 37, D, seed=2).to(dev), rnd(2, 37, D, seed=3).to(dev)
+        qka, va = leaves(qk, v)
+        o, w = ops.mha_self_packed(qka, va, None, scale)
+        o.backward(go)
+        (o2, w2), st = ops.mha_self_fwd_raw(qk, qk[:, :, D:], v, None, scale, False, True, 0.0, True)
+        assert w is None and w2 is None
+        _same_bits(o2, o.detach(), "mha packed out")
+        _same_bits(ops.mha_self_bwd_raw(st, go, None), (qka.grad, None, va.grad), "mha packed gradients")
+        (o3, _), st = ops.mha_self_fwd_raw(qk, qk[:, :, D:], v, None, scale, False, True, 0.0, False)
+        assert st is None
+        _same_bits(o3, o.detach(), "mha out without gradients")
+        qk, v, go, gw = (rnd(1, 8, n, seed=s).to(dev) for n, s in ((2 * D, 4), (D, 5), (D, 6), (8, 7)))
+        qka, va = leaves(qk, v)
+        o, w = ops.mha_self_packed(qka, va, None, scale, need_weights=True)
+        torch.autograd.backward([o, w], [go, gw])
+        (o2, w2), st = ops.mha_self_fwd_raw(qk, qk[:, :, D:], v, None, scale, True, True, 0.0, True)
+        _same_bits((o2, w2), (o.detach(), w.detach()), "mha weights out")
+        _same_bits(ops.mha_self_bwd_raw(st, go, gw), (qka.grad, None, va.grad), "mha weights gradients")
+        q, k, v, go = (rnd(2, 37, D, seed=s).to(dev) for s in (8, 9, 10, 11))
+        kpm = torch.zeros(2, 37, dtype=torch.bool)
+        kpm[0, 34:] = True
+        kpm[1, 1:4] = True
+        kpm = kpm.to(dev)
+        qa, ka, va = leaves(q, k, v)
+        o, _ = ops.mha_self(qa, ka, va, kpm, scale)
+        o.backward(go)
+        (o2, _), st = ops.mha_self_fwd_raw(q, k, v, kpm, scale, False, False, 0.0, True)
+        _same_bits(o2, o.detach(), "mha masked out")
+        _same_bits(ops.mha_self_bwd_raw(st, go, None), (qa.grad, ka.grad, va.grad), "mha masked gradients")
+        # ---- one-query cross-attention, with and without the second query / key part
+        q1, q2, go = (rnd(3, 256, seed=s).to(dev) for s in (1, 2, 6))
+        k1, k2, v = (rnd(3, 5, 256, seed=s).to(dev) for s in (3, 4, 5))
+        kpm = torch.zeros(3, 5, dtype=torch.bool)
+        kpm[0, 3:] = True
+        kpm = kpm.to(dev)
+        for two in (True, False):
+            ins = (q1, q2 if two else None, k1, k2 if two else None, v)
+            a = leaves(*ins)
+            out = ops.attn_q1(*a, kpm, 64 ** -0.5)
+            out.backward(go)
+            out2, st = ops.attn_q1_fwd_raw(*ins, kpm, 64 ** -0.5)
+            _same_bits(out2, out.detach(), f"q1 two={two} out")
+            _same_bits(ops.attn_q1_bwd_raw(st, go), [t.grad if t is not None else None for t in a], f"q1 two={two} gradients")
+        # ---- sine embedding of the anchors
+        anchor, gs = torch.sigmoid(rnd(3, 2, 4, seed=1)).to(dev), rnd(3, 2, 512, seed=2).to(dev)
+        (aa,) = leaves(anchor)
+        e = ops.sine_embed(aa)
+        e.backward(gs)
+        e2, st = ops.sine_embed_fwd_raw(anchor)
+        _same_bits(e2, e.detach(), "sine embedding")
+        _same_bits(ops.sine_embed_bwd_raw(st, gs), aa.grad, "sine embedding gradient")
+
 
 @both
 def _elementwise(dev, big):
