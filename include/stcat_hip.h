@@ -499,6 +499,15 @@ int stcat_grad_sqnorm_ws(const void* table, const int* chunk_tensor, const long*
 int stcat_adamw_ema_step(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                          const float* sqnorm, const float* lr, const float* wd, int n_groups, float beta1,
                          float beta2, float eps, int step, float max_norm, float ema_decay, void* stream);
+/* stcat_grad_accumulate: gradient accumulation over the micro-steps of one optimizer step.  Every table entry's
+ * accumulator (the m column; same length and memory layout as the gradient) takes the entry's gradient (the g column):
+ *   acc = (first ? g : acc + g) * scale
+ * first != 0 on the first micro-step of a window (an overwrite: the accumulator's old contents are never read), scale is
+ * 1 except on the last one, where fp32(1 / k) makes the sum over k micro-steps their mean.  One fp32 add, then one fp32
+ * multiply per element, no atomics: the same bits in and out of deterministic mode.  g is left unchanged.  n_chunks == 0
+ * is a no-op; a NULL table or chunk list, n_chunks < 0 or chunk <= 0 returns -1. */
+int stcat_grad_accumulate(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
+                          int first, float scale, void* stream);
 int stcat_grad_clip_scale(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                           const float* sqnorm, float max_norm, void* stream);
 int stcat_ema_update(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,

@@ -136,6 +136,39 @@ __global__ void __launch_bounds__(256) adamw_ema_kernel(const OptTensor* tab, co
   }
 }
 
+// Gradient accumulation (AdamW.accumulate): the accumulator of every table row (column m) takes the row's gradient
+// (column g): acc = (first ? g : acc + g) * scale.  `first` makes the window's first fold an overwrite — no memset, and
+// whatever an abandoned window left behind (a NaN included) is never read; `scale` is 1 except on the window's last fold,
+// where fp32(1 / k) turns the sum into the mean.  One fp32 add, then one fp32 multiply, one owner per element, no atomics:
+// the same left-to-right chain over the micro-steps in and out of deterministic mode.
+__global__ void __launch_bounds__(256) grad_accum_kernel(const OptTensor* tab, const int* chunk_tensor,
+                                                         const long* chunk_off, int chunk, int first, float scale) {
+  const OptTensor t = tab[chunk_tensor[blockIdx.x]];
+  const long lo = chunk_off[blockIdx.x];
+  const long hi = lo + chunk < t.n ? lo + chunk : t.n;
+  const float* g = t.g;
+  float* acc = t.m;
+  const bool vec = ((((unsigned long)(g + lo)) | ((unsigned long)(acc + lo))) & 15u) == 0;
+  if (vec) {
+    const long nv = lo + ((hi - lo) / 4) * 4;
+    for (long i = lo + (long)threadIdx.x * 4; i < nv; i += 256 * 4) {
+      const float4 g4 = stcat_ld4(g + i);
+      float4 a4 = g4;
+      if (!first) {
+        a4 = stcat_ld4(acc + i);
+        a4.x += g4.x; a4.y += g4.y; a4.z += g4.z; a4.w += g4.w;
+      }
+      a4.x *= scale; a4.y *= scale; a4.z *= scale; a4.w *= scale;
+      stcat_st4(acc + i, a4);
+    }
+    if (threadIdx.x == 0) {  // ragged tail (< 4 elements)
+      for (long j = nv; j < hi; ++j) acc[j] = (first ? g[j] : acc[j] + g[j]) * scale;
+    }
+  } else {
+    for (long i = lo + threadIdx.x; i < hi; i += 256) acc[i] = (first ? g[i] : acc[i] + g[i]) * scale;
+  }
+}
+
 // standalone clip_grad_norm_: g *= min(1, max_norm / (sqrt(sqnorm) + 1e-6)) over the tensor table, in place and
 // layout-agnostic (flat element order of each gradient buffer: row-major and channels_last alike)
 __global__ void __launch_bounds__(256) grad_clip_scale_kernel(const OptTensor* tab, const int* chunk_tensor,

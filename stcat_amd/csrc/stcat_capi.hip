@@ -1736,6 +1736,16 @@ int stcat_adamw_ema_step(const void* table, const int* chunk_tensor, const long*
   return launch_status();
 }
 
+int stcat_grad_accumulate(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
+                          int first, float scale, void* stream) {
+  if (!table || !chunk_tensor || !chunk_off) return fail("grad_accumulate: null tensor table or chunk list");
+  if (n_chunks < 0 || chunk <= 0) return fail("grad_accumulate: bad chunking (%d x %d)", n_chunks, chunk);
+  if (n_chunks == 0) return 0;
+  STCAT_LAUNCH(grad_accum_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const OptTensor*)table,
+               chunk_tensor, chunk_off, chunk, first ? 1 : 0, scale);
+  return launch_status();
+}
+
 int stcat_grad_clip_scale(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                           const float* sqnorm, float max_norm, void* stream) {
   if (n_chunks <= 0 || chunk <= 0) return fail("grad_clip_scale: bad chunking");

@@ -237,8 +237,9 @@ class GradBucketReducer:
                 # AccumulateGrad would; a bucket that was already reduced cannot take it any more
                 if b["pending"] < 0:
                     raise RuntimeError("GradBucketReducer.early: a bucket was already all-reduced when a second gradient "
-                                       "for one of its parameters arrived; call finish() between backward passes or "
-                                       "run gradient accumulation with STCAT_REDUCER_NO_OVERLAP=1")
+                                       "for one of its parameters arrived; call finish() between backward passes — for "
+                                       "gradient accumulation run every micro-step as a whole step (zero_grad, "
+                                       "backward, finish) and sum with stcat_amd.optim.AdamW.accumulate()")
                 if g.data_ptr() != self._view_of[p].data_ptr():   # (written through: the kernel accumulated in place)
                     again_s.append(g)
                     again_d.append(self._view_of[p])

@@ -104,6 +104,21 @@ class TrainStep:
         self.reducer.finish()
         return total
 
+    def window(self, optimizer, k: int, **step_kwargs):
+        """One optimizer step over `k` consecutive clips (gradient accumulation): k ordinary step()s — zero_grad, replayed
+        forward / backward, gradient exchange — the first k - 1 each followed by `optimizer.accumulate()`, the last by
+        `optimizer.step(**step_kwargs)`, which updates from the mean gradient.  Returns (the k loss totals, the squared
+        norm optimizer.step returned); no host sync.  Each total is copied: with launch plans the loss lives in a
+        static buffer that the next micro-step overwrites."""
+        if k < 1:
+            raise ValueError("TrainStep.window: k >= 1 micro-steps")
+        totals = []
+        for j in range(k):
+            totals.append(self.step().detach().clone())
+            if j < k - 1:
+                optimizer.accumulate()
+        return totals, optimizer.step(**step_kwargs)
+
     def gradients(self):
         return {n: p.grad.detach() for n, p in self.model.named_parameters() if p.grad is not None}
 

@@ -24,16 +24,19 @@ CHUNK = 1 << 16  # elements per workgroup
 
 
 class _TensorTable:
-    """Device table of (p, g, m, v, ema, n, group) entries + the chunk lists of csrc/optim.h.  Rebuilt only when a
-    pointer changes (gradient tensors are re-allocated by autograd unless they live in the reducer's flat buckets
-    or the zero arena, where they are stable from step to step)."""
+    """Device table of (p, g, m, v, ema, n, group) entries + the chunk lists of csrc/optim.h.  The rows are uploaded
+    again only when a pointer changes (gradient tensors are re-allocated by autograd unless they live in the reducer's
+    flat buckets, the zero arena or a launch plan's static buffers, where they are stable from step to step), the
+    chunk lists only when a tensor's length does."""
 
     def __init__(self, device):
         self.device = device
         self.key = None
+        self._sizes = None
         self.table = self.chunk_tensor = self.chunk_off = None
         self.n_chunks = 0
         self.partials = None
+        self.rebuilds = 0            # how often update() found a changed pointer (tools/bench_accum.py reports it)
         self.entry = L.load().stcat_optim_table_entry_bytes()
         assert self.entry == 56, self.entry
 
@@ -43,22 +46,39 @@ class _TensorTable:
         if key == self.key:
             return
         self.key = key
+        self.rebuilds += 1
         dt = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("ema", "<u8"), ("n", "<i8"),
                        ("group", "<i4"), ("pad", "<i4")])
         assert dt.itemsize == self.entry
-        tab = np.zeros(len(rows), dtype=dt)
-        ct, co = [], []
-        for i, (p, g, m, v, e, n, grp) in enumerate(rows):
-            tab[i] = (p, g, m, v, e, n, grp, 0)
-            for off in range(0, n, CHUNK):
-                ct.append(i)
-                co.append(off)
-        self.table = torch.from_numpy(tab.view(np.uint8).copy()).to(self.device)
-        self.chunk_tensor = torch.tensor(ct, dtype=torch.int32).to(self.device)
-        self.chunk_off = torch.tensor(co, dtype=torch.int64).to(self.device)
-        self.n_chunks = len(ct)
-        # one partial sum per chunk: the workspace of the ordered squared norm (stcat_grad_sqnorm_ws, deterministic mode)
-        self.partials = torch.empty(max(self.n_chunks, 1), dtype=torch.float32, device=self.device)
+        cols = np.array(rows, dtype=np.uint64).reshape(len(rows), 7)
+        sizes = tuple(r[5] for r in rows)
+        if sizes != self._sizes:
+            # the chunk lists depend on the tensors' lengths alone: built once, however often a pointer moves
+            self._sizes = sizes
+            ct, co = [], []
+            for i, n in enumerate(sizes):
+                for off in range(0, n, CHUNK):
+                    ct.append(i)
+                    co.append(off)
+            self.table = torch.empty(len(rows) * self.entry, dtype=torch.uint8, device=self.device)
+            self.chunk_tensor = torch.tensor(ct, dtype=torch.int32).to(self.device)
+            self.chunk_off = torch.tensor(co, dtype=torch.int64).to(self.device)
+            self.n_chunks = len(ct)
+            # one partial sum per chunk: the workspace of the ordered squared norm (stcat_grad_sqnorm_ws, deterministic mode)
+            self.partials = torch.empty(max(self.n_chunks, 1), dtype=torch.float32, device=self.device)
+        # A moved pointer (a gradient that autograd allocates afresh every step: two small tensors of the hot path) costs
+        # one stream-ordered copy of the rows from a pinned staging buffer — the host does not wait for the device, so a
+        # micro-step that ends in accumulate() leaves no bubble in front of the next one.  (The staging buffer is new each
+        # time: torch's pinned allocator does not hand it out again before the copy has run.)
+        pin = self.table.is_cuda
+        host = torch.empty(len(rows) * self.entry, dtype=torch.uint8, pin_memory=pin)
+        tab = host.numpy().view(dt)
+        for j, name in enumerate(("p", "g", "m", "v", "ema")):
+            tab[name] = cols[:, j]
+        tab["n"] = cols[:, 5].astype(np.int64)
+        tab["group"] = cols[:, 6].astype(np.int32)
+        tab["pad"] = 0
+        self.table.copy_(host, non_blocking=pin)
 
 
 def _dense(t: torch.Tensor) -> bool:
@@ -113,6 +133,15 @@ class AdamW:
         self._plist = [p for g in self.param_groups for p in g["params"]]
         self._gkey = None
         self._any = None
+        # gradient accumulation (accumulate()): one fp32 accumulator per parameter, allocated on first use and kept
+        self.param_names: Dict[torch.Tensor, str] = {}   # optional, for messages (make_optimizer fills it)
+        self._acc: Dict[torch.Tensor, torch.Tensor] = {}
+        self._acc_n = 0              # micro-steps folded into the open window (0: no window)
+        self._acc_set = None         # which parameters of _plist had a gradient at the window's first fold
+        self._acc_table = None       # rows (g = p.grad, m = accumulator), keyed on the gradient pointers
+        self._acc_gkey = None
+        self._win_table = None       # step()'s table with the g column on the accumulators
+        self._win_key = None
 
     def zero_grad(self, set_to_none: bool = True):
         for g in self.param_groups:
@@ -122,7 +151,8 @@ class AdamW:
                 elif p.grad is not None:
                     p.grad.zero_()
 
-    def _rows(self, ema_of):
+    def _rows(self, ema_of, from_acc: bool = False):
+        """from_acc: the g column points at the accumulators of the window instead of at p.grad"""
         rows = []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
@@ -136,36 +166,127 @@ class AdamW:
                 e = ema_of.get(p) if ema_of else None
                 if e is not None and not _same_layout(e, p):
                     raise L.StcatHipError("EMA tensor layout differs from its parameter")
-                rows.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                g = self._acc[p] if from_acc else p.grad
+                rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                              _ptr(e), p.numel(), gi))
         return rows
+
+    @staticmethod
+    def _ema_of(model_ema, model):
+        if model_ema is None:
+            return None
+        if model is None:
+            raise ValueError("model_ema needs the model it tracks")
+        ema_sd = dict(model_ema.named_parameters())
+        return {p: ema_sd[n] for n, p in model.named_parameters() if n in ema_sd}
+
+    # ---- gradient accumulation --------------------------------------------------------------------------------------
+    @property
+    def accumulated(self) -> int:
+        """micro-steps folded into the open accumulation window (0: no window is open)"""
+        return self._acc_n
+
+    def discard_accumulated(self) -> None:
+        """drop the open window; the accumulators stay allocated, their contents are never read again (the next
+        window's first fold overwrites them)"""
+        self._acc_n = 0
+        self._acc_set = None
+
+    def _name(self, p) -> str:
+        n = self.param_names.get(p)
+        if n is not None:
+            return n
+        i = next(i for i, q in enumerate(self._plist) if q is p)
+        return f"parameter {i} of the optimizer (shape {tuple(p.shape)})"
+
+    def _fold(self, scale: float) -> None:
+        """acc = (first fold of the window ? g : acc + g) * scale for every parameter with a gradient: ONE launch"""
+        plist = self._plist
+        gkey = tuple(p.grad.data_ptr() if p.grad is not None else 0 for p in plist)
+        have = tuple(k != 0 for k in gkey)
+        if self._acc_n and have != self._acc_set:
+            p = next(p for p, a, b in zip(plist, have, self._acc_set) if a != b)
+            raise ValueError(f"gradient accumulation: {self._name(p)} "
+                             f"{'has' if p.grad is not None else 'has no'} gradient in this micro-step, unlike in the "
+                             "window's first; every micro-step of a window must produce the same set of gradients "
+                             "(discard_accumulated() drops the window)")
+        if gkey != self._acc_gkey:
+            rows = []
+            for p in plist:
+                if p.grad is None:
+                    continue
+                L.check_tensor(p.grad, "gradient")
+                if p.grad.dtype != torch.float32 or not _dense(p) or not _same_layout(p.grad, p):
+                    raise L.StcatHipError("optimizer tensors must be dense fp32 and share one memory layout")
+                acc = self._acc.get(p)
+                if acc is None:
+                    acc = self._acc[p] = torch.empty_like(p)      # the parameter's own layout; first fold overwrites
+                rows.append((0, p.grad.data_ptr(), acc.data_ptr(), 0, 0, p.numel(), 0))
+            if not rows:
+                raise ValueError("gradient accumulation: no parameter has a gradient")
+            self._any = next(p for p in plist if p.grad is not None)
+            if self._acc_table is None:
+                self._acc_table = _TensorTable(self._any.device)
+            self._acc_table.update(rows)
+            self._acc_gkey = gkey
+        t = self._acc_table
+        L.call("stcat_grad_accumulate", t.table.data_ptr(), t.chunk_tensor.data_ptr(), t.chunk_off.data_ptr(),
+               t.n_chunks, CHUNK, 1 if self._acc_n == 0 else 0, float(np.float32(scale)), L.stream_of(self._any))
+        self._acc_set = have
+        self._acc_n += 1
+
+    @torch.no_grad()
+    def accumulate(self) -> None:
+        """Gradient accumulation: fold the current `p.grad` of every parameter that has one into the optimizer's fp32
+        accumulators (one multi-tensor launch on the current stream) and open — or extend — a window of micro-steps.
+        The next `step()` folds its own gradients too, scales the sum by 1 / (number of micro-steps) and updates from
+        that mean.  Call it where step() would be called (after the reducer's finish()); `p.grad` is left alone — the
+        loop's zero_grad at the top of the next micro-step resets it as in any other step, so every micro-step runs
+        the replayed launch plans and the overlapped gradient exchange unchanged:
+
+            for j in range(k):
+                reducer.zero_grad(); forward; backward; reducer.finish()
+                optimizer.accumulate() if j < k - 1 else optimizer.step(...)
+
+        The accumulators cost one more fp32 copy of the trainable parameters and are not checkpointed."""
+        self._fold(1.0)
 
     @torch.no_grad()
     def step(self, max_grad_norm: float = 0.0, model_ema=None, ema_decay: float = 0.0, model=None):
         """One optimizer step.  max_grad_norm > 0 clips by the global norm first (train_net.py:136-137); with
         `model_ema` (and the `model` it shadows) the EMA weights are updated in the same launch
-        (engine/optimizer.py:5-22).  Returns the squared gradient norm as a device scalar (no sync)."""
+        (engine/optimizer.py:5-22).  Returns the squared gradient norm as a device scalar (no sync).
+        With an accumulation window open (accumulate()), the current gradients are folded in as its last micro-step and
+        everything — clip, non-finite skip, moments, EMA, the returned squared norm — refers to the window's MEAN
+        gradient; the window is closed."""
         plist = self._plist
-        # cheap staleness key: the gradient pointers (everything else in the table is stable between steps)
-        gkey = (id(model_ema),) + tuple(p.grad.data_ptr() if p.grad is not None else 0 for p in plist)
-        if gkey != self._gkey:
-            ema_of = None
-            if model_ema is not None:
-                if model is None:
-                    raise ValueError("model_ema needs the model it tracks")
-                ema_sd = dict(model_ema.named_parameters())
-                ema_of = {p: ema_sd[n] for n, p in model.named_parameters() if n in ema_sd}
-            rows = self._rows(ema_of)
-            if not rows:
-                return None
-            self._any = next(p for p in plist if p.grad is not None)
-            if self._table is None:
-                self._table = _TensorTable(self._any.device)
-                self._sq = torch.zeros(1, device=self._any.device)
-            self._table.update(rows)
-            self._gkey = gkey
+        if self._acc_n:
+            self._fold(1.0 / (self._acc_n + 1))
+            self._acc_n = 0
+            self._acc_set = None
+            wkey = (id(model_ema),) + tuple(self._acc[p].data_ptr() if p.grad is not None else 0 for p in plist)
+            if wkey != self._win_key:
+                if self._win_table is None:
+                    self._win_table = _TensorTable(self._any.device)
+                self._win_table.update(self._rows(self._ema_of(model_ema, model), from_acc=True))
+                self._win_key = wkey
+            t = self._win_table
+        else:
+            # cheap staleness key: the gradient pointers (everything else in the table is stable between steps)
+            gkey = (id(model_ema),) + tuple(p.grad.data_ptr() if p.grad is not None else 0 for p in plist)
+            if gkey != self._gkey:
+                rows = self._rows(self._ema_of(model_ema, model))
+                if not rows:
+                    return None
+                self._any = next(p for p in plist if p.grad is not None)
+                if self._table is None:
+                    self._table = _TensorTable(self._any.device)
+                self._table.update(rows)
+                self._gkey = gkey
+            t = self._table
         any_p = self._any
-        t = self._table
+        if self._sq is None:
+            self._sq = torch.zeros(1, device=any_p.device)
         stream = L.stream_of(any_p)
         self.step_count += 1
         from . import ops
@@ -184,7 +305,11 @@ class AdamW:
 
     def state_dict(self):
         """torch.optim.AdamW's layout (what the reference's Checkpointer round-trips, utils/checkpoint.py):
-        state[idx] = {step, exp_avg, exp_avg_sq}, param_groups[i]["params"] = [idx, ...]."""
+        state[idx] = {step, exp_avg, exp_avg_sq}, param_groups[i]["params"] = [idx, ...].
+        The accumulators of an open accumulation window are not part of it: checkpoint between optimizer steps."""
+        if self._acc_n:
+            raise RuntimeError(f"AdamW.state_dict: an accumulation window is open ({self._acc_n} micro-steps folded) and "
+                               "accumulators are not checkpointed; call step() or discard_accumulated() first")
         idx, groups = {}, []
         for g in self.param_groups:
             ids = []
@@ -224,6 +349,8 @@ class AdamW:
         for g, saved in zip(self.param_groups, sd["param_groups"]):
             g.update({k: v for k, v in saved.items() if k != "params"})
         self._gkey = None
+        self._win_key = None         # (the moments were re-allocated: both step tables are stale)
+        self.discard_accumulated()
 
 
 def make_optimizer(cfg, model, logger=None) -> AdamW:
@@ -239,7 +366,9 @@ def make_optimizer(cfg, model, logger=None) -> AdamW:
         raise ValueError("stcat_amd.optim implements SOLVER.OPTIMIZER='adamw' only")
     groups = [{"params": rest}, {"params": vis, "lr": cfg.SOLVER.VIS_BACKBONE_LR},
               {"params": txt, "lr": cfg.SOLVER.TEXT_LR}, {"params": tmp, "lr": cfg.SOLVER.TEMP_LR}]
-    return AdamW(groups, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY)
+    opt = AdamW(groups, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY)
+    opt.param_names = {p: n for n, p in named}
+    return opt
 
 
 def adjust_learning_rate(cfg, optimizer, curr_step: int, num_training_steps: int) -> None:

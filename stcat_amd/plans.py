@@ -623,8 +623,9 @@ class PlannedFn(Function):
             if p.grad is not None and p.grad.data_ptr() in e.grad_ptrs:
                 raise L.StcatHipError(
                     "launch plan: a parameter's .grad still aliases the plan's static gradient buffer — reset gradients "
-                    "to None between steps (optimizer.zero_grad(set_to_none=True), PyTorch's default); gradient "
-                    "accumulation over several backward passes needs stcat_amd.plans.enable(False)")
+                    "to None between steps (optimizer.zero_grad(set_to_none=True), PyTorch's default); for gradient "
+                    "accumulation keep the zero_grad of every micro-step and call stcat_amd.optim.AdamW.accumulate() "
+                    "after each backward pass but the last")
         bkey = tuple(None if g is None else (tuple(g.shape), g.dtype) for g in gouts)
         ext = list(ctx.ext) + [g for g in gouts]
         got = e.bwd.get(bkey)
