@@ -452,6 +452,12 @@ int stcat_pl_rowscale(void* h, void* l, const float* w, long rows, int C, int pe
  * out / in with stride % 4 == 0 take the float4 path, anything else a scalar one.  No atomics: the same form in and out of
  * deterministic mode. */
 int stcat_rank_sum(float* out, const float* in, int n_ranks, long n, long stride, float scale, void* stream);
+/* The same sum as a balanced tree (the canonical window, stcat_amd.set_canonical_window): adjacent pairs in rank order,
+ *   n_ranks = 4: ((in0 + in1) + (in2 + in3)) * scale,   n_ranks = 8: (((in0 + in1) + (in2 + in3)) + ((in4 + in5) + (in6 + in7))) * scale
+ * (one multiply after the last add; every slice is loaded before the first add).  n_ranks is 1, 2, 4 or 8 — anything else
+ * returns -1 — n >= 0, stride >= n.  One float4 form: out and in 16-byte aligned and stride % 4 == 0, else -1.  out may be
+ * exactly one of the slices; any other overlap is refused.  Nothing is written when a call is refused. */
+int stcat_rank_tree_sum(float* out, const float* in, int n_ranks, long n, long stride, float scale, void* stream);
 
 /* ---- VideoSTGLoss (models/criterion.py:11-208), all decoder layers in one launch --------------------------------
  * vec[k*nl + l] = un-weighted loss k of decoder layer l; k = 0 loss_bbox (criterion.py:38-55), 1 loss_giou (:56-66),
@@ -508,6 +514,16 @@ int stcat_adamw_ema_step(const void* table, const int* chunk_tensor, const long*
  * is a no-op; a NULL table or chunk list, n_chunks < 0 or chunk <= 0 returns -1. */
 int stcat_grad_accumulate(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                           int first, float scale, void* stream);
+/* stcat_grad_tree_fold: the canonical window's form of stcat_grad_accumulate — the micro-steps of one optimizer step
+ * added as a balanced binary tree (a binary counter over per-row level buffers) instead of a chain.  A table row holds
+ * the gradient in the g column and the level buffers 0, 1, 2, 3 in the p, m, v, ema columns (a window of k = 2^q
+ * micro-steps uses the first q).  For the 0-based micro-step j, n_carry = the number of trailing one bits of j:
+ *   carry = g;  carry = level[i] + carry  for i = 0 .. n_carry - 1  (fp32, in this order, all loads first)
+ * last == 0: level[n_carry] = carry.  last != 0 (the window's last micro-step, n_carry == q >= 1): level[q - 1] =
+ * carry * scale, in place.  g is left unchanged; no level is ever cleared.  0 <= n_carry <= 4; last with n_carry == 0,
+ * n_carry == 4 without last, a NULL table or chunk list, n_chunks < 0 or chunk <= 0 return -1; n_chunks == 0 is a no-op. */
+int stcat_grad_tree_fold(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
+                         int n_carry, int last, float scale, void* stream);
 int stcat_grad_clip_scale(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                           const float* sqnorm, float max_norm, void* stream);
 int stcat_ema_update(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,

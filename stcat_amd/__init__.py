@@ -31,6 +31,18 @@ def is_deterministic() -> bool:
     return _lib.is_deterministic()
 
 
+def set_canonical_window(n) -> None:
+    """The canonical window of `n` clips per optimizer step — the same bits for every split of the clips over ranks and
+    micro-steps; None turns it off (see stcat_amd._lib.set_canonical_window)."""
+    from . import _lib
+    _lib.set_canonical_window(n)
+
+
+def canonical_window():
+    from . import _lib
+    return _lib.canonical_window()
+
+
 def install(text_encoder: bool = False):
     """Rebind the reference's factory seam.  Requires the reference package ``models``
     to be importable; must run before ``STCATNet`` is constructed.  ``text_encoder=True`` also rebinds

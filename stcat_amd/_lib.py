@@ -125,6 +125,70 @@ def deterministic_requested() -> bool:
     return os.environ.get("STCAT_DETERMINISTIC", "") not in ("", "0")
 
 
+_UNSET = object()
+_window = _UNSET              # set_canonical_window's argument; _UNSET: STCAT_CANONICAL_WINDOW decides
+_window_env = (None, None)    # (the variable's text, what it parsed to)
+WINDOW_MAX = 128              # clips of one canonical window: world <= 8 ranks (stcat_rank_tree_sum) x k <= 16 micro-steps
+
+
+def _check_window(n, what: str) -> int:
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1 or n & (n - 1) or n > WINDOW_MAX:
+        raise ValueError(f"{what}={n!r}: the canonical window is a power of two of clips, 1 .. {WINDOW_MAX}")
+    return n
+
+
+def set_canonical_window(n: Optional[int]) -> None:
+    """The canonical window (opt-in, needs deterministic mode): `n` clips per optimizer step, a power of two that the
+    world size divides.  While it is on, the mean gradient of an optimizer step is ONE fp32 expression over the clips
+    c = 0 .. n - 1 of the step — the balanced binary tree ((g0 + g1) + (g2 + g3)) + ..., times fp32(1 / n) once — whatever
+    the split into ranks and micro-steps (clip c = micro-step * world + rank), so a run gives the same weights on 1, 2, 4 or
+    8 GPUs: the ordered exchange adds the ranks with stcat_rank_tree_sum at every world size from two, AdamW.accumulate() /
+    step() add the micro-steps with stcat_grad_tree_fold, the dropout seed leaves the rank out and its counters follow the
+    global clip number (ops.dropout_begin_step(device, clip=...)), and TrainStep.window normalises the loss by the window's
+    box count.  `None` turns it off (STCAT_CANONICAL_WINDOW=n is what holds when this was never called).  The setting is
+    part of the launch-plan signature."""
+    global _window
+    if n is not None:
+        _check_window(n, "set_canonical_window: n")
+        if not deterministic_requested():
+            raise ValueError("set_canonical_window: the canonical window needs deterministic mode "
+                             "(stcat_amd.set_deterministic(True) or STCAT_DETERMINISTIC=1) — without it the kernels "
+                             "of a step add in an order of their own and no layout repeats even itself")
+    _window = n
+
+
+def canonical_window() -> Optional[int]:
+    """the canonical window's clip count, None: off.  Does not load the kernel library."""
+    global _window_env
+    n = _window
+    if n is _UNSET:
+        env = os.environ.get("STCAT_CANONICAL_WINDOW", "")
+        if env != _window_env[0]:
+            if env in ("", "0"):
+                _window_env = (env, None)
+            else:
+                if not env.isdigit():
+                    raise ValueError(f"STCAT_CANONICAL_WINDOW={env!r}: expected a number of clips")
+                _window_env = (env, _check_window(int(env), "STCAT_CANONICAL_WINDOW"))
+        n = _window_env[1]
+    if n is not None and not deterministic_requested():
+        raise ValueError(f"canonical window of {n} clips: it needs deterministic mode, which is off "
+                         "(stcat_amd.set_deterministic(True) or STCAT_DETERMINISTIC=1)")
+    return n
+
+
+def window_micro_steps(world: int) -> Optional[int]:
+    """k = N / world of the canonical window (None: the mode is off); a world that does not divide N is refused"""
+    n = canonical_window()
+    if n is None:
+        return None
+    if world < 1 or n % world:
+        raise ValueError(f"canonical window of {n} clips: the world size {world} does not divide it")
+    if n // world > 16:
+        raise ValueError(f"canonical window of {n} clips on {world} rank(s): {n // world} micro-steps (at most 16)")
+    return n // world
+
+
 def f16_grad_scale() -> float:
     """factor carried by every GRADIENT plane in mode f16x3p (1.0 in every other mode): tools / op tests that build
     gradient planes themselves multiply by it; the product path scales where gradients enter the backbone (pl_act_bwd)"""

@@ -71,10 +71,12 @@
   X(stcat_rowscale, "ppliis") \
   X(stcat_pl_rowscale, "pppliis") \
   X(stcat_rank_sum, "ppillfs") \
+  X(stcat_rank_tree_sum, "ppillfs") \
   X(stcat_grad_sqnorm, "pppiips") \
   X(stcat_grad_sqnorm_ws, "pppiippls") \
   X(stcat_adamw_ema_step, "pppiipPPifffiffs") \
   X(stcat_grad_accumulate, "pppiiifs") \
+  X(stcat_grad_tree_fold, "pppiiiifs") \
   X(stcat_grad_clip_scale, "pppiipfs") \
   X(stcat_ema_update, "pppiifs") \
   X(stcat_optim_table_entry_bytes, "") \

@@ -18,6 +18,7 @@
 #include "clip_transform.h"
 #include "pointwise.h"
 #include "rank_sum.h"
+#include "canonical_tree.h"
 #include "loss.h"
 #include "text_encoder.h"
 
@@ -1746,6 +1747,34 @@ int stcat_grad_accumulate(const void* table, const int* chunk_tensor, const long
   return launch_status();
 }
 
+// One micro-step of the canonical window's binary-counter fold (canonical_tree.h): n_carry = trailing one bits of the
+// 0-based micro-step = the levels consumed; `last` (the window's last micro-step) multiplies by scale and writes in
+// place into the top level consumed, otherwise the result opens level n_carry.
+int stcat_grad_tree_fold(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
+                         int n_carry, int last, float scale, void* stream) {
+  if (!table || !chunk_tensor || !chunk_off) return fail("grad_tree_fold: null tensor table or chunk list");
+  if (n_chunks < 0 || chunk <= 0) return fail("grad_tree_fold: bad chunking (%d x %d)", n_chunks, chunk);
+  if (n_carry < 0 || n_carry > GRAD_TREE_LEVELS)
+    return fail("grad_tree_fold: n_carry=%d (0 .. %d: a window has at most %d micro-steps)", n_carry, GRAD_TREE_LEVELS,
+                1 << GRAD_TREE_LEVELS);
+  if (last && n_carry == 0) return fail("grad_tree_fold: last with n_carry=0 (a window of one micro-step has nothing to fold)");
+  if (!last && n_carry == GRAD_TREE_LEVELS)
+    return fail("grad_tree_fold: n_carry=%d opens level %d, which no table row has", n_carry, GRAD_TREE_LEVELS);
+  if (n_chunks == 0) return 0;
+#define STCAT_FOLD(NC)                                                                                                \
+  STCAT_LAUNCH(grad_tree_fold_kernel<NC>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const OptTensor*)table, \
+               chunk_tensor, chunk_off, chunk, last ? 1 : 0, scale)
+  switch (n_carry) {
+    case 0: STCAT_FOLD(0); break;
+    case 1: STCAT_FOLD(1); break;
+    case 2: STCAT_FOLD(2); break;
+    case 3: STCAT_FOLD(3); break;
+    default: STCAT_FOLD(4); break;
+  }
+#undef STCAT_FOLD
+  return launch_status();
+}
+
 int stcat_grad_clip_scale(const void* table, const int* chunk_tensor, const long* chunk_off, int n_chunks, int chunk,
                           const float* sqnorm, float max_norm, void* stream) {
   if (n_chunks <= 0 || chunk <= 0) return fail("grad_clip_scale: bad chunking");
@@ -2206,6 +2235,38 @@ int stcat_rank_sum(float* out, const float* in, int n_ranks, long n, long stride
   else
     STCAT_LAUNCH(rank_sum_kernel<false>, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, out, in, n_ranks, n,
                  stride, scale);
+  return launch_status();
+}
+
+// The cross-rank sum of the canonical window (canonical_tree.h): the adjacent-pair tree over the slices in rank order,
+// times scale.  Operands and overlap as stcat_rank_sum; there is one (float4) form, so what that entry point sends down
+// its scalar path — out or in off a 16-byte boundary, stride % 4 != 0 — is refused here.
+int stcat_rank_tree_sum(float* out, const float* in, int n_ranks, long n, long stride, float scale, void* stream) {
+  if (!out) return fail("rank_tree_sum: out is null");
+  if (!in) return fail("rank_tree_sum: in is null");
+  if (n_ranks < 1 || n_ranks > RANK_TREE_MAX || (n_ranks & (n_ranks - 1)))
+    return fail("rank_tree_sum: n_ranks=%d (a power of two up to %d)", n_ranks, RANK_TREE_MAX);
+  if (n < 0) return fail("rank_tree_sum: n=%ld is negative", n);
+  if (stride < n) return fail("rank_tree_sum: stride=%ld is less than n=%ld (the slices would overlap)", stride, n);
+  if (stride % 4 != 0) return fail("rank_tree_sum: stride=%ld is no multiple of 4 floats (slices must be 16-byte aligned)", stride);
+  if (!aligned16(out) || !aligned16(in)) return fail("rank_tree_sum: out and in must be 16-byte aligned");
+  if (n == 0) return 0;
+  const uintptr_t o = reinterpret_cast<uintptr_t>(out), bytes = (uintptr_t)n * 4;
+  for (int k = 0; k < n_ranks; ++k) {
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in) + (uintptr_t)k * (uintptr_t)stride * 4;
+    if (o != s && o < s + bytes && s < o + bytes)
+      return fail("rank_tree_sum: out overlaps slice %d of in without being that slice (out == in + k * stride is the only alias allowed)", k);
+  }
+  const dim3 grid(grid_for(n >> 2, 256, 2048));
+#define STCAT_TREE(NR) \
+  STCAT_LAUNCH(rank_tree_kernel<NR>, grid, dim3(256), 0, (hipStream_t)stream, out, in, n, stride, scale)
+  switch (n_ranks) {
+    case 1: STCAT_TREE(1); break;
+    case 2: STCAT_TREE(2); break;
+    case 4: STCAT_TREE(4); break;
+    default: STCAT_TREE(8); break;
+  }
+#undef STCAT_TREE
   return launch_status();
 }
 

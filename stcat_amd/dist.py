@@ -65,7 +65,8 @@ class GradBucketReducer:
         """extra_numel: a dummy tail bucket (e.g. 124.6 M elements to emulate the reference's RoBERTa gradients
         in the message size) — reduced with the rest, never read.
         ordered: the rank-ordered exchange (all-to-all, stcat_rank_sum, all-gather) instead of the summing collective;
-        None: STCAT_DP_ORDERED (1 / 0), else on exactly when world > 2 in deterministic mode."""
+        None: STCAT_DP_ORDERED (1 / 0), else on exactly when world > 2 in deterministic mode.  With a canonical window
+        (stcat_amd.set_canonical_window) it is on from two ranks and sums with stcat_rank_tree_sum."""
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
@@ -122,18 +123,36 @@ class GradBucketReducer:
         # The ordered exchange replaces either of them (`collective` keeps its meaning: what runs when it is off).  A sum of
         # two operands has one order, so up to two ranks nothing changes unless it is asked for; the question "is the mode
         # on" is answered without loading the kernel library (a reducer over gloo on CPU tensors has none to load).
+        refused = ordered is False
         if ordered is None:
             env = os.environ.get("STCAT_DP_ORDERED", "")
             if env not in ("", "0", "1"):
                 raise ValueError(f"STCAT_DP_ORDERED={env!r}: expected 1 or 0")
+            refused = env == "0"
             ordered = (env == "1") if env else (self.world > 2 and _lib.deterministic_requested())
+        # The canonical window (stcat_amd.set_canonical_window): the ranks of a micro-step are the lower log2(world) levels
+        # of the window's tree, so the ordered exchange runs at every world size from two (a summing collective has no
+        # scale-free sum to offer) with stcat_rank_tree_sum, and the tree's one multiply by fp32(1 / N) sits here only when
+        # this sum is its last add (k = 1 micro-step); otherwise AdamW's fold applies it.
+        self.window_k = _lib.window_micro_steps(self.world)
+        if self.window_k is not None and self.world > 1:
+            if refused:
+                raise ValueError("GradBucketReducer: the canonical window needs the ordered exchange (ordered=False / "
+                                 "STCAT_DP_ORDERED=0 was asked for)")
+            ordered = True
         self.ordered = bool(ordered) and self.comm
         self._exchange_stream = None     # the stream the ordered exchange is issued on (created with the first bucket)
         self._owner = {}
         pad_to = 64 * max(self.world, 1)      # a flat bucket splits into `world` equal, 256-byte aligned shards
+        # Canonical window: every parameter's slot starts on a 16-byte boundary, like a gradient tensor of its own.  With one
+        # micro-step the optimizer reads the mean gradient from these views, with several from its level buffers (separate
+        # allocations): its kernels choose their float4 or scalar form — not the same fp32 expression once the compiler has
+        # contracted each — by the pointers' alignment, which must therefore not depend on the layout.
+        slot = 4 if self.window_k is not None else 1
         for bi, b in enumerate(self.buckets):
             dev = b["params"][0][1].device
-            b["padded"] = -(-b["numel"] // pad_to) * pad_to
+            extent = sum(-(-p.numel() // slot) * slot for _, p in b["params"])
+            b["padded"] = -(-extent // pad_to) * pad_to
             # the flat communication buffer only exists when there is somebody to talk to
             b["flat"] = torch.zeros(b["padded"], dtype=torch.float32, device=dev) if self.comm else None
             b["shard"] = (torch.empty(b["padded"] // self.world, dtype=torch.float32, device=dev)
@@ -152,7 +171,7 @@ class GradBucketReducer:
                     # keep the parameter's memory format (conv weights are channels_last)
                     cl = p.dim() == 4 and not p.is_contiguous() and p.is_contiguous(memory_format=torch.channels_last)
                     b["views"].append(torch.as_strided(view, p.shape, p.stride()) if cl else view.view(p.shape))
-                off += p.numel()
+                off += -(-p.numel() // slot) * slot
                 self._owner[p] = bi
                 p.register_post_accumulate_grad_hook(self._on_grad)
             b["pending"] = len(b["params"])
@@ -330,10 +349,14 @@ class GradBucketReducer:
         S = flat.numel() // self.world
         mine = flat[self.rank * S:(self.rank + 1) * S]
         scale = 1.0 / self.world
+        entry = "stcat_rank_sum"
+        if self.window_k is not None:
+            entry = "stcat_rank_tree_sum"
+            scale = 1.0 / self.world if self.window_k == 1 else 1.0
 
         def run():
             dist.all_to_all_single(recv, flat, group=self.group, async_op=True).wait()
-            _lib.call("stcat_rank_sum", mine.data_ptr(), recv.data_ptr(), self.world, S, S, scale, _lib.stream_of(flat))
+            _lib.call(entry, mine.data_ptr(), recv.data_ptr(), self.world, S, S, scale, _lib.stream_of(flat))
             return dist.all_gather_into_tensor(flat, mine, group=self.group, async_op=True)
 
         _lib.check_tensor(flat, "gradient bucket")

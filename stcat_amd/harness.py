@@ -9,10 +9,30 @@ from __future__ import annotations
 
 import torch
 
-from . import ops, plans, synth
+from . import _lib, ops, plans, synth
 from .dist import GradBucketReducer
 from .misc import BoxList, NestedTensor
 from .pipeline import SyntheticText, build_model
+
+
+def window_num_boxes(counts, n_clips: int, dev, out=None):
+    """The loss normaliser of a canonical window (stcat_amd.set_canonical_window): `counts` are the box counts of the clips
+    THIS rank runs in the window; their integer sum is all-reduced once (exact in any order) and
+    clamp(total / n_clips, 1) comes back as a 1-element fp32 device tensor (written into `out` when given) — the mean box
+    count over the window's clips, the same value for every split of them over ranks and micro-steps, and with one
+    micro-step the reference's own normaliser (criterion.py:175-178).  No host sync."""
+    import torch.distributed as dist
+    cuda = torch.device(dev).type == "cuda"
+    host = torch.empty(1, dtype=torch.int64, pin_memory=cuda)
+    host[0] = int(sum(counts))
+    total = host.to(dev, non_blocking=True) if cuda else host
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(total)
+    nb = torch.clamp(total.to(torch.float32) / float(n_clips), min=1)
+    if out is None:
+        return nb
+    out.copy_(nb)
+    return out
 
 
 class TrainStep:
@@ -25,7 +45,7 @@ class TrainStep:
 
     def __init__(self, dev, config="C3", rank: int = 0, train: bool = True, roberta_dummy: bool = False,
                  force_comm: bool = False, clip=None, targets=None, loss_plan_inside: bool = True, seed: int = 20260929,
-                 arena_elems: int = 120_000_000, clips=None, pipeline_prefix: bool = False):
+                 arena_elems: int = 120_000_000, clips=None, pipeline_prefix: bool = False, clip_targets=None):
         self.dev = dev
         T, res, L = synth.CONFIGS[config] if isinstance(config, str) else config
         self.T, self.res, self.L = T, res, L
@@ -59,6 +79,18 @@ class TrainStep:
             targets = [{"actioness": act, "boxs": BoxList(tb)}]
         self.targets_host = targets                      # annotations as the loader holds them (host memory)
         self.targets = [{"actioness": t["actioness"].to(dev), "boxs": t["boxs"].to(dev)} for t in targets]
+        # `clip_targets`: the annotations of each of `clips` (one target list per clip); without it every clip is paired
+        # with `targets`
+        if clip_targets is not None and len(clip_targets) != len(self.clips):
+            raise ValueError(f"TrainStep: {len(clip_targets)} target lists for {len(self.clips)} clips")
+        self.clip_targets_host = clip_targets
+        self.clip_targets = None if clip_targets is None else [
+            [{"actioness": t["actioness"].to(dev), "boxs": t["boxs"].to(dev)} for t in ts] for ts in clip_targets]
+        # canonical window (window()): optimizer steps taken, the global clip number of the micro-step under way, the
+        # window's loss normaliser (one device scalar, kept: the loss node's launch plan holds its address)
+        self.window_index = 0
+        self._clip_number = None
+        self._window_nb = None
         self.loss_plan_inside = loss_plan_inside
         self._plan = None
         self.uniform_w = len({self.wd[k] for k in self.wd if k.startswith("loss_bbox")}) == 1
@@ -67,7 +99,9 @@ class TrainStep:
 
     # ---- the loss's target-only tensors ---------------------------------------------------------------------------
     def loss_plan(self):
-        if self.loss_plan_inside or self._plan is None:
+        if self._clip_number is not None:
+            self._plan = self.criterion.plan(self.targets_host, [self.T], self.dev, num_boxes=self._window_nb)
+        elif self.loss_plan_inside or self._plan is None:
             self._plan = self.criterion.plan(self.targets_host, [self.T], self.dev)
             self._plan.num_boxes(self.dev)               # criterion.py:175-178: the 1-element all-reduce (no host sync)
         return self._plan
@@ -75,7 +109,14 @@ class TrainStep:
     # ---- one video: forward + loss + backward; no host syncs ------------------------------------------------------
     def compute(self):
         dev = self.dev
-        ops.dropout_begin_step(dev)
+        if self._clip_number is not None:    # canonical window: the clip and its dropout masks follow its global number
+            ops.dropout_begin_step(dev, clip=self._clip_number)
+            self.clip_index = self._clip_number
+        else:
+            ops.dropout_begin_step(dev)
+        if self.clip_targets is not None:
+            i = self.clip_index % len(self.clips)
+            self.targets_host, self.targets = self.clip_targets_host[i], self.clip_targets[i]
         self.arena.reset()
         # training updates the fp32 weights between steps, so the per-step split of all conv weights into bf16 planes
         # (+ the transposed, FrozenBN-scaled copies for the data gradients) is part of every step: no optimizer runs
@@ -85,7 +126,9 @@ class TrainStep:
         self.videos = self.clips[self.clip_index % len(self.clips)]
         self.clip_index += 1
         if self.pipeline_prefix:
-            nxt = self.clips[self.clip_index % len(self.clips)]
+            # (canonical window: this rank's next clip is world numbers on, within the window and across its end)
+            nxt_i = self.clip_index if self._clip_number is None else self._clip_number + self.reducer.world
+            nxt = self.clips[nxt_i % len(self.clips)]
             self.model.vis_encoder[0].stage_next(nxt.tensors)
         out = self.model(self.videos, ["synthetic"])
         if self.keep_outputs:        # (tests: the criterion overwrites pred_boxes with the GT-span rows, criterion.py:168-171)
@@ -109,14 +152,47 @@ class TrainStep:
         forward / backward, gradient exchange — the first k - 1 each followed by `optimizer.accumulate()`, the last by
         `optimizer.step(**step_kwargs)`, which updates from the mean gradient.  Returns (the k loss totals, the squared
         norm optimizer.step returned); no host sync.  Each total is copied: with launch plans the loss lives in a
-        static buffer that the next micro-step overwrites."""
+        static buffer that the next micro-step overwrites.
+        With a canonical window of N clips (stcat_amd.set_canonical_window, set before this object is built) k must be
+        N / world, and micro-step m of the s-th window runs global clip G = s * N + m * world + rank — clips[G % len(clips)]
+        with its clip_targets, what a DistributedSampler over the shared list hands out — with the dropout counters of clip G
+        and the loss normalised by the window's box count (window_num_boxes): the update is then bit for bit the same for
+        every world size that divides N."""
         if k < 1:
             raise ValueError("TrainStep.window: k >= 1 micro-steps")
+        n_win = _lib.canonical_window()
+        if n_win is not None:
+            return self._canonical_window(optimizer, k, n_win, step_kwargs)
         totals = []
         for j in range(k):
             totals.append(self.step().detach().clone())
             if j < k - 1:
                 optimizer.accumulate()
+        return totals, optimizer.step(**step_kwargs)
+
+    def _canonical_window(self, optimizer, k, n_win, step_kwargs):
+        world, rank = self.reducer.world, self.reducer.rank
+        want = _lib.window_micro_steps(world)
+        if k != want:
+            raise ValueError(f"TrainStep.window: k={k}, but the canonical window of {n_win} clips is {want} micro-steps "
+                             f"on {world} rank(s)")
+        numbers = [self.window_index * n_win + m * world + rank for m in range(k)]
+        tg = self.clip_targets_host
+        counts = [sum(len(t["boxs"]) for t in (tg[g % len(self.clips)] if tg is not None else self.targets_host))
+                  for g in numbers]
+        if self._window_nb is None:
+            self._window_nb = torch.empty(1, dtype=torch.float32, device=self.dev)
+        window_num_boxes(counts, n_win, self.dev, out=self._window_nb)
+        totals = []
+        try:
+            for m, g in enumerate(numbers):
+                self._clip_number = g
+                totals.append(self.step().detach().clone())
+                if m < k - 1:
+                    optimizer.accumulate()
+        finally:
+            self._clip_number = None
+        self.window_index += 1
         return totals, optimizer.step(**step_kwargs)
 
     def gradients(self):

@@ -858,6 +858,8 @@ class _DropoutStream:
                 rank = dist.get_rank()
         except Exception:
             pass
+        if L.canonical_window() is not None:
+            rank = 0     # canonical window: which rank runs a clip must not show in its masks (manual_seed)
         return _mix_seed(torch.initial_seed() & _MASK64, rank)
 
     def _words(self, device) -> torch.Tensor:
@@ -884,18 +886,30 @@ class _DropoutStream:
             raise RuntimeError("dropout counter range of one step exhausted (2^36 decisions in one forward pass)")
         return self.seed, off, self.base(device).data_ptr()
 
-    def begin_step(self, device):
+    def begin_step(self, device, clip: Optional[int] = None):
         """Open a new counter range.  The master word advances in place (stream-ordered, capturable: a replayed
         hipGraph draws fresh masks), then lands in the slot the next forward's kernels read.  The slot only moves on
         when the previous forward's backward is still outstanding (gradient accumulation over several clips, two
         losses): that backward regenerates its masks from ITS slot, which this step must not touch.  A plain
-        forward / backward loop stays on one slot, so launch arguments are identical from step to step."""
-        self.offset = 0
+        forward / backward loop stays on one slot, so launch arguments are identical from step to step.
+        clip = G (the canonical window): the master word is SET to (G + 1) * STEP_SPAN — a stream-ordered fill, the launch
+        arguments stay what they were — so the masks of global clip G are the same whichever rank and micro-step runs it.
+        A captured hipGraph would replay that constant, the same masks for every clip: refused there."""
         w = self._words(device)
         capturing = w.is_cuda and torch.cuda.is_current_stream_capturing()
+        if clip is not None:
+            if capturing:
+                raise RuntimeError("dropout_begin_step(clip=...) inside a hipGraph capture: the clip number would be baked "
+                                   "into the graph and every replay would draw the same masks")
+            if not 0 <= clip < (1 << 63) // self.STEP_SPAN - 1:
+                raise ValueError(f"dropout_begin_step: clip={clip} is outside the counter range")
+        self.offset = 0
         if self.pending and not capturing:
             self._slot[device] = (self._slot[device] + 1) % self.SLOTS
-        w[0:1].add_(self.STEP_SPAN)
+        if clip is not None:
+            w[0:1].fill_((clip + 1) * self.STEP_SPAN)
+        else:
+            w[0:1].add_(self.STEP_SPAN)
         self.base(device).copy_(w[0:1])
 
     def auto_begin_step(self, device):
@@ -917,7 +931,11 @@ def _mix_seed(seed: int, rank: int) -> int:
 
 
 def manual_seed(seed: int, rank: int = 0) -> None:
-    """Seed the dropout stream of this process (counters restart at 0)."""
+    """Seed the dropout stream of this process (counters restart at 0).  With a canonical window
+    (stcat_amd.set_canonical_window) the rank is left out of the seed: a clip's masks follow its global number
+    (dropout_begin_step(device, clip=...)), not the rank that happens to run it."""
+    if L.canonical_window() is not None:
+        rank = 0
     _dropout_stream.seed = _mix_seed(seed, rank)
     _dropout_stream.offset = 0
     _dropout_stream.pending = False
@@ -926,9 +944,11 @@ def manual_seed(seed: int, rank: int = 0) -> None:
         _dropout_stream._slot[d] = 0
 
 
-def dropout_begin_step(device) -> None:
-    """Call once at the top of every training step (inside the captured region when the step is a hipGraph)."""
-    _dropout_stream.begin_step(torch.device(device))
+def dropout_begin_step(device, clip: Optional[int] = None) -> None:
+    """Call once at the top of every training step (inside the captured region when the step is a hipGraph).
+    clip: the global clip number s * N + m * world + r of the canonical window (optimizer step s, micro-step m, rank r) —
+    the counter range is then that clip's own instead of the next one of this process; not inside a hipGraph capture."""
+    _dropout_stream.begin_step(torch.device(device), clip)
 
 
 def dropout_auto_begin_step(device) -> None:

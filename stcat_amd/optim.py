@@ -142,6 +142,11 @@ class AdamW:
         self._acc_gkey = None
         self._win_table = None       # step()'s table with the g column on the accumulators
         self._win_key = None
+        # canonical window (stcat_amd.set_canonical_window): the micro-steps are added as a balanced tree — a binary
+        # counter over log2(k) fp32 level buffers per parameter, allocated on first use and kept
+        self._levels: Dict[torch.Tensor, List[torch.Tensor]] = {}
+        self._tree_table = None      # rows (g = p.grad, p / m / v / ema = levels 0 .. 3)
+        self._tree_key = None
 
     def zero_grad(self, set_to_none: bool = True):
         for g in self.param_groups:
@@ -151,8 +156,8 @@ class AdamW:
                 elif p.grad is not None:
                     p.grad.zero_()
 
-    def _rows(self, ema_of, from_acc: bool = False):
-        """from_acc: the g column points at the accumulators of the window instead of at p.grad"""
+    def _rows(self, ema_of, src=None):
+        """src (parameter -> tensor): the g column points at the window's mean gradient there instead of at p.grad"""
         rows = []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
@@ -166,7 +171,7 @@ class AdamW:
                 e = ema_of.get(p) if ema_of else None
                 if e is not None and not _same_layout(e, p):
                     raise L.StcatHipError("EMA tensor layout differs from its parameter")
-                g = self._acc[p] if from_acc else p.grad
+                g = src[p] if src is not None else p.grad
                 rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                              _ptr(e), p.numel(), gi))
         return rows
@@ -199,8 +204,8 @@ class AdamW:
         i = next(i for i, q in enumerate(self._plist) if q is p)
         return f"parameter {i} of the optimizer (shape {tuple(p.shape)})"
 
-    def _fold(self, scale: float) -> None:
-        """acc = (first fold of the window ? g : acc + g) * scale for every parameter with a gradient: ONE launch"""
+    def _grad_key(self):
+        """(the gradient pointers, which parameters have one); inside a window the set must be the first fold's"""
         plist = self._plist
         gkey = tuple(p.grad.data_ptr() if p.grad is not None else 0 for p in plist)
         have = tuple(k != 0 for k in gkey)
@@ -210,6 +215,12 @@ class AdamW:
                              f"{'has' if p.grad is not None else 'has no'} gradient in this micro-step, unlike in the "
                              "window's first; every micro-step of a window must produce the same set of gradients "
                              "(discard_accumulated() drops the window)")
+        return gkey, have
+
+    def _fold(self, scale: float) -> None:
+        """acc = (first fold of the window ? g : acc + g) * scale for every parameter with a gradient: ONE launch"""
+        plist = self._plist
+        gkey, have = self._grad_key()
         if gkey != self._acc_gkey:
             rows = []
             for p in plist:
@@ -235,6 +246,57 @@ class AdamW:
         self._acc_set = have
         self._acc_n += 1
 
+    @staticmethod
+    def _tree_k() -> Optional[int]:
+        """micro-steps per optimizer step of the canonical window on this world size; None: the mode is off"""
+        if L.canonical_window() is None:
+            return None
+        import torch.distributed as dist
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        return L.window_micro_steps(world)
+
+    def _fold_tree(self, k: int, last: bool):
+        """micro-step j = self._acc_n of a canonical window of k: carry = g, carry = level[i] + carry for the trailing
+        one bits i of j, into level[number of them] — on the last micro-step times fp32(1 / N) in place into the top
+        level, which is returned per parameter (where step() reads the mean gradient).  ONE launch."""
+        j = self._acc_n
+        if not last and j + 1 >= k:
+            raise ValueError(f"AdamW.accumulate: the canonical window has {k} micro-steps per optimizer step on this "
+                             f"world size and {j} are folded: micro-step {j + 1} belongs to step(), which closes the window")
+        q = k.bit_length() - 1
+        n_carry = (~j & (j + 1)).bit_length() - 1          # trailing one bits of j
+        assert q <= 4 and (n_carry == q if last else n_carry < q), (k, j, last)
+        plist = self._plist
+        gkey, have = self._grad_key()
+        key = (q,) + gkey
+        if key != self._tree_key:
+            rows = []
+            for p in plist:
+                if p.grad is None:
+                    continue
+                L.check_tensor(p.grad, "gradient")
+                if p.grad.dtype != torch.float32 or not _dense(p) or not _same_layout(p.grad, p):
+                    raise L.StcatHipError("optimizer tensors must be dense fp32 and share one memory layout")
+                lv = self._levels.setdefault(p, [])
+                while len(lv) < q:
+                    lv.append(torch.empty_like(p))             # the parameter's own layout; never cleared, never read first
+                ptrs = [lv[i].data_ptr() if i < q else 0 for i in range(4)]
+                rows.append((ptrs[0], p.grad.data_ptr(), ptrs[1], ptrs[2], ptrs[3], p.numel(), 0))
+            if not rows:
+                raise ValueError("gradient accumulation: no parameter has a gradient")
+            self._any = next(p for p in plist if p.grad is not None)
+            if self._tree_table is None:
+                self._tree_table = _TensorTable(self._any.device)
+            self._tree_table.update(rows)
+            self._tree_key = key
+        t = self._tree_table
+        scale = float(np.float32(1.0) / np.float32(L.canonical_window())) if last else 1.0
+        L.call("stcat_grad_tree_fold", t.table.data_ptr(), t.chunk_tensor.data_ptr(), t.chunk_off.data_ptr(),
+               t.n_chunks, CHUNK, n_carry, 1 if last else 0, scale, L.stream_of(self._any))
+        self._acc_set = have
+        self._acc_n += 1
+        return {p: self._levels[p][q - 1] for p in plist if p.grad is not None} if last else None
+
     @torch.no_grad()
     def accumulate(self) -> None:
         """Gradient accumulation: fold the current `p.grad` of every parameter that has one into the optimizer's fp32
@@ -248,8 +310,15 @@ class AdamW:
                 reducer.zero_grad(); forward; backward; reducer.finish()
                 optimizer.accumulate() if j < k - 1 else optimizer.step(...)
 
-        The accumulators cost one more fp32 copy of the trainable parameters and are not checkpointed."""
-        self._fold(1.0)
+        The accumulators cost one more fp32 copy of the trainable parameters and are not checkpointed.
+        With a canonical window (stcat_amd.set_canonical_window(N)) the micro-steps are added as a balanced binary tree
+        (stcat_grad_tree_fold) through log2(k) level buffers per parameter, k = N / world, and step() multiplies by
+        fp32(1 / N): the mean is then the same fp32 expression over the window's N clips on every world size."""
+        tree_k = self._tree_k()
+        if tree_k is not None:
+            self._fold_tree(tree_k, last=False)
+        else:
+            self._fold(1.0)
 
     @torch.no_grad()
     def step(self, max_grad_norm: float = 0.0, model_ema=None, ema_decay: float = 0.0, model=None):
@@ -260,7 +329,24 @@ class AdamW:
         everything — clip, non-finite skip, moments, EMA, the returned squared norm — refers to the window's MEAN
         gradient; the window is closed."""
         plist = self._plist
-        if self._acc_n:
+        tree_k = self._tree_k()
+        if tree_k is not None and (tree_k > 1 or self._acc_n):
+            # canonical window: exactly k = N / world folds, this one included — the tree has no other shape
+            if self._acc_n + 1 != tree_k:
+                raise ValueError(f"AdamW.step: the canonical window has {tree_k} micro-steps per optimizer step on this "
+                                 f"world size, and this step would close it after {self._acc_n + 1} "
+                                 "(discard_accumulated() drops the open window)")
+            top = self._fold_tree(tree_k, last=True)
+            self._acc_n = 0
+            self._acc_set = None
+            wkey = (id(model_ema), "tree") + tuple(top[p].data_ptr() if p.grad is not None else 0 for p in plist)
+            if wkey != self._win_key:
+                if self._win_table is None:
+                    self._win_table = _TensorTable(self._any.device)
+                self._win_table.update(self._rows(self._ema_of(model_ema, model), src=top))
+                self._win_key = wkey
+            t = self._win_table
+        elif self._acc_n:
             self._fold(1.0 / (self._acc_n + 1))
             self._acc_n = 0
             self._acc_set = None
@@ -268,7 +354,7 @@ class AdamW:
             if wkey != self._win_key:
                 if self._win_table is None:
                     self._win_table = _TensorTable(self._any.device)
-                self._win_table.update(self._rows(self._ema_of(model_ema, model), from_acc=True))
+                self._win_table.update(self._rows(self._ema_of(model_ema, model), src=self._acc))
                 self._win_key = wkey
             t = self._win_table
         else:

@@ -123,7 +123,9 @@ class LossPlan:
     actioness weights), built once per batch on the host side of the input pipeline — the reference recomputes
     it inside the loss with device->host syncs (criterion.py:160-192), which stalls the launch queue."""
 
-    def __init__(self, targets, durations, device, sigma: float, eos_coef: float):
+    def __init__(self, targets, durations, device, sigma: float, eos_coef: float, num_boxes=None):
+        """num_boxes: a normaliser decided outside (the canonical window's: the box count of the whole window over its N
+        clips, a device scalar — harness.window_num_boxes); num_boxes() then returns it and runs no collective"""
         T = max(durations)
         b = len(durations)
         self.T, self.b = T, b
@@ -134,7 +136,7 @@ class LossPlan:
             rows.extend(range(i * T + on[0], i * T + on[-1] + 1))
         self.bounds = bounds
         self.num_boxes_local = float(sum(len(t["boxs"]) for t in targets))
-        self._num_boxes = None
+        self._num_boxes = num_boxes
         time_mask = torch.zeros(b, T, dtype=torch.bool)
         positive = torch.zeros(b, T, dtype=torch.bool)
         weight = torch.full((b, T), eos_coef)
@@ -194,7 +196,8 @@ class LossPlan:
     def num_boxes(self, dev):
         """criterion.py:175-178: box count averaged over ranks, clamped to >= 1.  It depends on the targets only,
         so the 1-element all-reduce runs ONCE here, when the plan is first used — not inside every loss
-        evaluation (which keeps the loss free of collectives and capturable in a hipGraph)."""
+        evaluation (which keeps the loss free of collectives and capturable in a hipGraph).  A plan built with
+        `num_boxes=` returns that value instead."""
         if self._num_boxes is None:
             if torch.distributed.is_available() and torch.distributed.is_initialized():
                 nb = torch.as_tensor([self.num_boxes_local], dtype=torch.float, device=dev)
@@ -220,8 +223,8 @@ class VideoSTGLoss(nn.Module):
         self._wmat_cache = None
         self._last = None
 
-    def plan(self, targets, durations, device) -> LossPlan:
-        return LossPlan(targets, durations, device, self.sigma, self.eos_coef)
+    def plan(self, targets, durations, device, num_boxes=None) -> LossPlan:
+        return LossPlan(targets, durations, device, self.sigma, self.eos_coef, num_boxes=num_boxes)
 
     def _wmat(self, nl: int, dev):
         """weight_dict laid out like the kernel's vec [5][nl] (row k = ops.LOSS_ROWS[k]; column nl-1 = the main output,

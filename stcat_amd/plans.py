@@ -231,7 +231,8 @@ class Recorder:
         # +3.4 ms per step at one rank, profiles/r06_prefix_pipeline.log — every N > 1 run since the watch became
         # unconditional in round 4 carried that.)
         # For the same reason nothing the action launches through the library belongs in the plan: recording is suspended
-        # around it.  (The ordered exchange runs stcat_rank_sum from here; mirrored into the plan, every replay would run a
+        # around it.  (The ordered exchange runs stcat_rank_sum — stcat_rank_tree_sum
+        # with a canonical window — from here; mirrored into the plan, every replay would run a
         # stale copy of the sum with baked pointers at the yield point — racing the all-to-all that fills its input —
         # besides the real one the action issues.)
         prev, self.allow_foreign = self.allow_foreign, True
@@ -469,7 +470,7 @@ def _global_sig(dev):
     ds = ops._dropout_stream
     base = ds.base(dev).data_ptr() if dev in ds._base else 0
     return (L.get_mma_mode(), L.is_deterministic(), STATIC_EPOCH, ds.offset, ds.seed, base, id(ops.GRAD_SINK), ops.FORK_ENABLED,
-            ops.WGRAD_STREAM_ENABLED, ops.MHA_BS_LONG)
+            ops.WGRAD_STREAM_ENABLED, ops.MHA_BS_LONG, L.canonical_window())
 
 
 def _record(dev, ext, pool, body):

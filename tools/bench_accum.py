@@ -9,11 +9,20 @@ pipelined prefix on — spans of four clips and one optimizer step, three loops,
       Timed only if it arrives at (B)'s gradients (checked first, from one seed); otherwise the log says why not.
 
     python tools/bench_accum.py [--reps 20] [--warmup 3] [--config C3] [--k 4]
+    python tools/bench_accum.py --canonical [...]      # the canonical-window leg instead (below)
 
 Prints median / min / max per variant, (B - A) per micro-step with the bytes per second the folds would have reached had
 they alone made the difference (a fold moves 12 B per element, 8 B the first of a window), the fold timed on its own,
 and for (C) whether (B) is faster by more than the larger min-max spread.  Every learning rate is 0, so all spans see
-the same weights; the optimizer's launches do not depend on the values."""
+the same weights; the optimizer's launches do not depend on the values.
+
+--canonical: what the canonical window (stcat_amd.set_canonical_window) costs — deterministic mode on throughout, one
+rank, alternating in ONE process:
+  (D) TrainStep.window(optimizer, k) with the window off: the deterministic window as it was before the mode existed
+      (stcat_grad_accumulate: one accumulator, a chain);
+  (E) the same with set_canonical_window(k): stcat_grad_tree_fold through log2(k) level buffers, the dropout counters set
+      from the clip number, the loss normalised by the window's box count (one device scalar).
+Prints median / min / max of both and whether (E) - (D) exceeds the larger min-max spread."""
 import argparse
 import os
 import statistics
@@ -30,14 +39,85 @@ from stcat_amd.harness import TrainStep  # noqa: E402
 SEED = 4242
 
 
+def canonical_leg(a):
+    import stcat_amd
+    k = a.k
+    L.load()
+    L.set_mma_mode("bf16x6p")
+    L.set_deterministic(True)
+    dev = torch.device("cuda:0")
+    T, res, _ = synth.CONFIGS[a.config]
+    clips = [(synth.synth_frames(T, res, seed=3000 + 500 * j), torch.zeros(T, res, res, dtype=torch.bool)) for j in range(2)]
+    plans.enable(True)
+    ts = TrainStep(dev, a.config, train=True, clips=clips, pipeline_prefix=True)
+    # one optimizer per variant (every learning rate is 0): neither re-uploads its step table because the other ran
+    opts = {w: optim.AdamW([p for p in ts.model.parameters() if p.requires_grad], lr=0.0, weight_decay=0.0) for w in (None, k)}
+    kw = dict(max_grad_norm=0.1)
+
+    def span(window):
+        stcat_amd.set_canonical_window(window)
+        ts.window(opts[window], k, **kw)
+
+    variants = {"D": None, "E": k}
+    for _ in range(3):                      # eager, recorded, replayed — under either plan signature
+        for w in variants.values():
+            span(w)
+    torch.cuda.synchronize()
+    elems = sum(t.numel() for t in opts[None]._acc.values())
+    levels = sum(t.numel() for lv in opts[k]._levels.values() for t in lv)
+    print(f"canonical window: {a.config}, bf16x6p, train mode, deterministic mode, plans on, pipelined prefix, one rank, "
+          f"window(k={k}) + 1 optimizer step per span; (D) {4 * elems / 1e6:.0f} MB of accumulators, (E) {4 * levels / 1e6:.0f} MB "
+          f"of level buffers; {a.reps} alternating repetitions after {a.warmup} warm-up; {torch.cuda.get_device_name(0)}")
+
+    def counters():
+        return {key: plans.STATS.get(key, 0) for key in ("eager", "recorded", "refused")}
+
+    times = {name: [] for name in variants}
+    host = {name: [] for name in variants}
+    moved_on = {name: {} for name in variants}
+    for rep in range(a.warmup + a.reps):
+        for name, w in variants.items():                             # alternating: D, E, D, E, ...
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            c0, t0 = counters(), time.perf_counter()
+            e0.record()
+            span(w)
+            e1.record()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                times[name].append(e0.elapsed_time(e1))
+                host[name].append((t1 - t0) * 1e3)
+                for key, v in counters().items():
+                    moved_on[name][key] = moved_on[name].get(key, 0) + v - c0[key]
+    stcat_amd.set_canonical_window(None)
+    stats = {}
+    for name, v in times.items():
+        med, lo, hi = statistics.median(v), min(v), max(v)
+        stats[name] = (med, lo, hi)
+        print(f"({name}) median {med:9.3f} ms per span  (min {lo:.3f}, max {hi:.3f}, spread {hi - lo:.3f})  "
+              f"{med / k:8.3f} ms per clip;  host done after {statistics.median(host[name]):.1f} ms;  over the timed spans: "
+              + ", ".join(f"{key} {v}" for key, v in moved_on[name].items()))
+    gap = stats["E"][0] - stats["D"][0]
+    spread = max(stats["D"][2] - stats["D"][1], stats["E"][2] - stats["E"][1])
+    print(f"(E) - (D) = {gap:+.3f} ms per span = {gap / k:+.3f} ms per micro-step ({stats['E'][0] / stats['D'][0]:.4f}x); "
+          f"larger min-max spread {spread:.3f} ms per span")
+    print(f"the difference exceeds the spread: {'yes' if abs(gap) > spread else 'no'}")
+    ts.close()
+    L.set_deterministic(False)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3")
     ap.add_argument("--k", type=int, default=4)
+    ap.add_argument("--canonical", action="store_true", help="time the canonical window against the plain deterministic one")
     a = ap.parse_args()
     assert a.reps >= 1 and a.k >= 2 and torch.cuda.is_available(), "needs the GPU"
+    if a.canonical:
+        return canonical_leg(a)
     L.load()
     L.set_mma_mode("bf16x6p")
     dev = torch.device("cuda:0")
